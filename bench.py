@@ -22,6 +22,11 @@ Precision (``--precision``, default fp32 = the reference's, lab/tutorial_1a/hfl_
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     torchrun --nproc-per-node 8 bench.py --gpus 8 ...
+
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` rounds, print
+one JSON line (``ms_per_step`` = wall milliseconds per timed round). ``--dump-outputs DIR`` also
+writes what the last timed round computed as ``DIR/<name>.npy`` (same arguments -> same inputs, so
+two builds can be compared array for array); ``--full`` adds the untimed extras (test accuracy).
 """
 from __future__ import annotations
 
@@ -40,6 +45,25 @@ METRIC = "FedAvg rounds/sec + local samples/sec, ResNet-18 CIFAR-10-shape, 8 cli
 # the same config, timed on one MI355X with stock PyTorch-ROCm (benchmarks/bench_reference_eager.py
 # --variant faithful; profiles/reference_eager_r3.jsonl).
 REFERENCE_SAMPLES_PER_S = {"fp32": 5296.8}
+
+
+def _dump_outputs(out_dir, fl):
+    """What a caller of the timed path holds after its last round, as float32 ``<name>.npy`` files
+    (under 64 MB in all): the server model (``w_global``, ``b_global``) and the rows of this
+    rank's client slots as local training left them (``client_weights``). An array above its
+    share of the budget is written as a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budgets = {"w_global": 48 << 20, "b_global": 4 << 20, "client_weights": 8 << 20}
+    arrays = {"w_global": fl.w_global, "b_global": fl.b_global,
+              "client_weights": fl.net.store.data[:fl.slots]}
+    for name, t in arrays.items():
+        t = t.detach().to(torch.float32)
+        n = budgets[name] // 4
+        if t.numel() > n:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), n))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def main():
@@ -65,9 +89,20 @@ def main():
     ap.add_argument("--deterministic", action="store_true",
                     help="require a bitwise-reproducible run (the fp32 path: no float atomics; two runs "
                          "print the same w_global_sha256)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds, write what the last round computed as DIR/<name>.npy "
+                         "(float32): the server weights and BN buffers, and a seeded sample of the "
+                         "clients' locally trained weights")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure (untimed): today the test "
+                         "accuracy of --eval. A plain run only sets up, warms up and times the rounds")
     args = ap.parse_args()
     if args.deterministic and args.precision != "fp32":
         ap.error("--deterministic needs --precision fp32 (the bf16 path reduces with float atomics)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed FedAvg rounds)")
+    if args.full:
+        args.eval = True
 
     from ddl25spring_amd.runtime import dist as rdist
     ctx = rdist.init(backend=args.backend)
@@ -114,6 +149,9 @@ def main():
     ms_per_round = 1000.0 * elapsed / args.steps
     samples_per_s = samples / elapsed
     rounds_per_s = args.steps / elapsed
+    if args.dump_outputs and ctx.is_main:
+        # before the evaluation, which reloads the server model into client slot 0
+        _dump_outputs(args.dump_outputs, fl)
     acc = fl.test() if args.eval else None
     w_hash = hashlib.sha256(fl.w_global.detach().cpu().numpy().tobytes()).hexdigest()
     hashes = [w_hash]

@@ -6,6 +6,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+# the heart-disease table the tabular tests train on: the copy stored with the suite, so that every
+# machine (and every process a test starts) reads the same rows
+os.environ.setdefault("DDL_HEART_CSV", os.path.join(ROOT, "tests", "golden", "heart.csv"))
 
 
 def pytest_configure(config):

@@ -83,13 +83,26 @@ def test_rccl_world1_collectives_and_bucketers(cuda):
 
 def test_bench_over_world1_rccl(cuda):
     """bench.py with its collectives on RCCL (world-1 nccl group): aggregation all-reduce, device
-    barrier and max-over-ranks timing all go through RCCL."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-                        "--train-size", "4000"], capture_output=True, text=True, timeout=600, cwd=ROOT,
-                       env=_env(29812))
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1 and json.loads(lines[0])["dtype"] == "fp32", r.stdout[-2000:]
+    barrier and max-over-ranks timing all go through RCCL. With --dump-outputs the run also leaves
+    the last round's arrays as float32 .npy files: the server weights it hashed, the BN buffers and
+    the sample of the clients' rows, within the 64 MB budget."""
+    import hashlib
+
+    import numpy as np
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
+                            "--train-size", "4000", "--dump-outputs", d], capture_output=True, text=True,
+                           timeout=600, cwd=ROOT, env=_env(29812))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["dtype"] == "fp32", r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 1 and out["ms_per_step"] > 0, out
+        assert sorted(os.listdir(d)) == ["b_global.npy", "client_weights.npy", "w_global.npy"]
+        arrays = {n[:-4]: np.load(os.path.join(d, n)) for n in os.listdir(d)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    assert hashlib.sha256(arrays["w_global"].tobytes()).hexdigest() == out["w_global_sha256"]
 
 
 def _pp_worker(rank, world, port, schedule, out, precision):
