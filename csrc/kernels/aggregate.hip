@@ -227,8 +227,11 @@ __device__ __forceinline__ void bitonic_sort(float (&v)[KP]) {
         const int l = i ^ j;
         if (l > i) {
           const bool up = ((i & k) == 0);
-          const float a = v[i], b = v[l];
-          if ((a > b) == up) { v[i] = b; v[l] = a; }
+          // min / max, not compare + two selects: the callers hand over NaN-free values, for
+          // which this is the same exchange in two instructions (and fewer live registers)
+          const float lo = fminf(v[i], v[l]), hi = fmaxf(v[i], v[l]);
+          v[i] = up ? lo : hi;
+          v[l] = up ? hi : lo;
         }
       }
     }
@@ -252,7 +255,8 @@ __device__ __forceinline__ void bitonic_merge(float (&v)[N]) {
   }
 }
 
-// Register-resident sort of KP <= 128 values. Above 64 the network is split: two 64-sorts, one
+// Register-resident sort of KP <= 128 values, none of them a NaN (fminf / fmaxf drop a NaN and
+// duplicate its partner: callers canonicalise first). Above 64 the network is split: two 64-sorts, one
 // cross compare (a[i] vs b[63-i] leaves every a <= every b, both halves bitonic) and two 64-merges,
 // so each unrolled loop nest stays small enough to be fully unrolled and the array never leaves
 // VGPRs (a single 128-wide network is only partially unrolled and falls back to scratch memory).
@@ -288,7 +292,11 @@ __global__ __launch_bounds__(256) void coord_select_kernel(const float* __restri
     const float* p = X + e;  // walk the rows by pointer increments: no per-row 64-bit offsets
 #pragma unroll
     for (int i = 0; i < KP; ++i) {
-      v[i] = (i < K) ? *p : INFINITY;
+      // a NaN orders as +inf (canonicalised here, on load): the networks' compares and fminf /
+      // fmaxf are a total order only without NaNs -- with one the array came back unsorted, or the
+      // NaN was dropped and its partner duplicated
+      const float x = (i < K) ? *p : INFINITY;
+      v[i] = (x == x) ? x : INFINITY;
       p += (i + 1 < K) ? ld : 0;
     }
     sort_values<KP>(v);
@@ -355,8 +363,9 @@ DDL_API int ddl_pack_shards(const float* rows, long long ld, int G, long long P,
 }
 
 // Krum (Blanchard et al. 2017) from the K x K Gram of the client updates: d2[i][j] = g_ii + g_jj -
-// 2 g_ij (clamped at 0), score_i = sum of the nb smallest d2[i][j], j != i (ascending order, as a
-// sort would add them), sel = the m clients of least score (exact ties to the smaller key: the
+// 2 g_ij (clamped at 0; not finite counts as +inf, so a row holding a NaN / Inf entry is infinitely
+// far from everyone), score_i = sum of the nb smallest d2[i][j], j != i (ascending order, as a
+// sort would add them), sel = the min(m, K) clients of least score (exact ties to the smaller key: the
 // client's global order, so the choice does not depend on the rank layout; default the index). One block, a thread per
 // client: its row sorted in registers by the bitonic network above.
 template <int KP>
@@ -372,7 +381,13 @@ __global__ __launch_bounds__(128) void krum_select_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
       float d = INFINITY;
-      if (j < K && j != i) d = fmaxf(gii + gram[j * K + j] - 2.f * gram[i * K + j], 0.f);
+      if (j < K && j != i) {
+        // a distance that is not finite (a NaN / Inf entry in either row, or an fp32 Gram that
+        // overflowed) counts as +inf: fmaxf alone returns its non-NaN operand, which put a NaN row
+        // at distance 0 from everybody
+        const float t = gii + gram[j * K + j] - 2.f * gram[i * K + j];
+        d = (fabsf(t) < INFINITY) ? fmaxf(t, 0.f) : INFINITY;
+      }
       v[j] = d;
     }
     sort_values<KP>(v);
@@ -385,6 +400,8 @@ __global__ __launch_bounds__(128) void krum_select_kernel(const float* __restric
   }
   __syncthreads();
   if (i < K) {
+    // every distance is in [0, +inf], so a score is never NaN: at worst +inf, which ranks last
+    // (ties among +inf scores by key, like any other tie)
     const float s = sc[i];
     int rank = 0;
     const int ki = keys ? keys[i] : i;
@@ -395,7 +412,8 @@ __global__ __launch_bounds__(128) void krum_select_kernel(const float* __restric
 
 DDL_API int ddl_krum_select(const float* gram, int K, int nb, int m, const int* keys, float* scores, int* sel,
                             hipStream_t st) {
-  if (K < 1 || K > 128 || nb < 1 || nb > K - 1 + (K == 1) || m < 1 || m > K) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > 128 || nb < 1 || nb > K - 1 + (K == 1) || m < 1) return (int)hipErrorInvalidValue;
+  if (m > K) m = K;  // multi-Krum with fewer clients than m selects them all: sel[0 .. K-1] written
 #define KRUM_CASE(KP_) \
   if (K <= KP_) { \
     hipLaunchKernelGGL(krum_select_kernel<KP_>, dim3(1), dim3(128), 0, st, gram, K, nb, m, keys, scores, sel); \

@@ -131,7 +131,9 @@ class TrimmedMean(_Sharded):
 
 
 class Krum(_Sharded):
-    """Krum (m=1) / multi-Krum (m>1) with f assumed Byzantine clients."""
+    """Krum (m=1) / multi-Krum (m>1) with f assumed Byzantine clients. A row with a NaN / Inf entry
+    (or one large enough to overflow the fp32 Gram) is infinitely far from everyone and ranks last;
+    m is clamped to the number of clients (``Fn.krum_select``)."""
     name = "krum"
 
     def __init__(self, f: int = 1, m: int = 1):
@@ -148,24 +150,21 @@ class Krum(_Sharded):
         if ctx.is_distributed:
             ctx.all_reduce(gram)
         nb = max(1, K - self.f - 2)
-        m = max(1, self.m)
+        m = min(max(1, self.m), K)  # multi-Krum with fewer clients than m averages them all
         if K <= Fn.MAX_ROBUST_CLIENTS:
             # scores, selection and the winners' mean on the device: krum_select + mean_rows_idx
             # (aggregate.hip), no torch sort / argsort / index_select glue
             _, sel = Fn.krum_select(gram.contiguous(), nb, m, keys)
             self._sel = sel  # stays on the device: no host sync per round (``last_selected`` reads it)
             return self.unshard(ctx, Fn.mean_rows_idx(shard, sel), P, Pp)
-        sq = torch.diagonal(gram)
-        d2 = (sq[:, None] + sq[None, :] - 2 * gram).clamp_min(0)
-        d2.fill_diagonal_(float("inf"))
-        scores = torch.sort(d2, 1).values[:, :nb].sum(1)
-        kk = torch.arange(K, device=scores.device) if keys is None else torch.tensor(keys, device=scores.device)
-        order = sorted(range(K), key=lambda i: (float(scores[i]), int(kk[i])))  # K > 128 only
-        sel = torch.tensor(order[:m], dtype=torch.long, device=scores.device)
+        # K > 128 only: the kernel's rules in torch (non-finite distances far, ties by key)
+        _, order = Fn.krum_rank(gram, nb, m, keys)
+        sel = torch.tensor(order, dtype=torch.long, device=gram.device)
         self._sel = sel
         chosen = shard.index_select(0, sel)
         part = torch.empty(chosen.shape[1], dtype=torch.float32, device=chosen.device)
-        Fn.weighted_sum(chosen, torch.full((m,), 1.0 / m, dtype=torch.float32, device=chosen.device), part)
+        n_sel = sel.numel()  # one weight per row actually selected
+        Fn.weighted_sum(chosen, torch.full((n_sel,), 1.0 / n_sel, dtype=torch.float32, device=chosen.device), part)
         return self.unshard(ctx, part, P, Pp)
 
     @property

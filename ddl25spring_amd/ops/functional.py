@@ -10,6 +10,7 @@ Layout contract (see csrc/include/ddl_common.h):
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 
 import torch
@@ -1393,20 +1394,42 @@ def pack_shards(rows, W: int, S: int, gmax: int, out=None):
     return out
 
 
-def krum_select(gram, nb: int, m: int, keys=None):
-    """Krum scores (sum of the nb smallest squared distances to the other clients) from a K x K Gram,
-    and the m clients of least score -> (scores [K] fp32, sel [m] int32 row indices). Exact ties go
-    to the smaller key (``keys``: a per-row int list, default the row index)."""
+def krum_rank(gram, nb: int, m: int, keys=None):
+    """Krum in plain torch from a K x K Gram, on the Gram's device: the CPU twin of the
+    ``krum_select`` kernel and the rule for K > MAX_ROBUST_CLIENTS -> (scores [K], order[:min(m, K)]
+    as a list). Same rules as the kernel: a squared distance that is not finite counts as +inf,
+    a score that is not finite ranks last, ties go to the smaller key."""
     K = gram.shape[0]
     if keys is None:
         keys = list(range(K))
+    inf = float("inf")
+    sq = torch.diagonal(gram)
+    d2 = sq[:, None] + sq[None, :] - 2 * gram
+    d2 = torch.where(torch.isfinite(d2), d2.clamp_min(0), torch.full_like(d2, inf))
+    d2.fill_diagonal_(inf)
+    scores = torch.sort(d2, 1).values[:, :nb].sum(1)
+    rank_by = [s if math.isfinite(s) else inf for s in scores.tolist()]
+    order = sorted(range(K), key=lambda i: (rank_by[i], int(keys[i])))
+    return scores, order[:min(m, K)]
+
+
+def krum_select(gram, nb: int, m: int, keys=None):
+    """Krum scores (sum of the nb smallest squared distances to the other clients) from a K x K Gram,
+    and the min(m, K) clients of least score -> (scores [K] fp32, sel [min(m, K)] int32 row indices).
+
+    * d2[i][j] = g_ii + g_jj - 2 g_ij clamped at 0; a d2 that is not finite (a NaN / Inf entry in
+      either row, or an fp32 Gram that overflowed) counts as +inf: such a row is infinitely far from
+      everyone, never at distance 0.
+    * A score that is not finite ranks last (as +inf).
+    * ``m`` is clamped to K (multi-Krum with fewer clients than m averages them all).
+    * Exact ties go to the smaller key (``keys``: a per-row int list, default the row index)."""
+    K = gram.shape[0]
+    if keys is None:
+        keys = list(range(K))
+    m = min(m, K)
     if not gram.is_cuda:
-        sq = torch.diagonal(gram)
-        d2 = (sq[:, None] + sq[None, :] - 2 * gram).clamp_min(0)
-        d2.fill_diagonal_(float("inf"))
-        scores = torch.sort(d2, 1).values[:, :nb].sum(1)
-        order = sorted(range(K), key=lambda i: (float(scores[i]), keys[i]))
-        return scores, torch.tensor(order[:m], dtype=torch.int32)
+        scores, order = krum_rank(gram, nb, m, keys)
+        return scores, torch.tensor(order, dtype=torch.int32)
     assert gram.dtype == torch.float32 and gram.is_contiguous() and K <= MAX_ROBUST_CLIENTS
     scores = torch.empty(K, dtype=torch.float32, device=gram.device)
     sel = torch.empty(m, dtype=torch.int32, device=gram.device)
@@ -1436,9 +1459,15 @@ def mean_rows_idx(X, sel, out=None):
 
 
 def coord_select(X, mode: str, trim: int = 0):
-    """Coordinate-wise median ('median') or trimmed mean ('trimmed') over K rows of X [K, n]."""
+    """Coordinate-wise median ('median') or trimmed mean ('trimmed') over K rows of X [K, n].
+
+    The K values of a coordinate are sorted with a NaN ordered (and counted) as +inf; -inf and +inf
+    order as themselves. Median: 0.5 * (s[(K-1)//2] + s[K//2]); trimmed mean: the mean of
+    s[trim : K-trim]. So up to (K-1)//2 (median) or ``trim`` (trimmed mean) rows of NaN / Inf
+    entries per coordinate leave the result inside the range of the other rows."""
     m = 0 if mode == "median" else 1
     if not X.is_cuda:
+        X = torch.where(torch.isnan(X), torch.full_like(X, float("inf")), X)
         return ref.coord_select(X, m, trim)
     _robust_k(X.shape[0], f"coord_select({mode})")
     assert X.dtype == torch.float32 and X.stride(1) == 1

@@ -359,6 +359,7 @@ def test_aggregation(cuda):
     sh = torch.zeros(G, P + 7, dtype=torch.bfloat16, device=cuda)
     Fn.broadcast_rows(out, dst[:, :P], sh[:, :P])
     assert torch.equal(dst[:, :P], out.expand(G, P)) and dst[:, P:].abs().max() == 0
+    assert torch.equal(sh[:, :P].cpu(), out.cpu().to(torch.bfloat16).expand(G, P)) and sh[:, P:].float().abs().max() == 0
     for K in (3, 8, 20, 33, 64, 65, 100, 128):
         X = torch.randn(K, 20000, device=cuda)
         c = torch.randn(20000, device=cuda)
