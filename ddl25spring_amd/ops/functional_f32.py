@@ -668,41 +668,55 @@ def conv_dgrad(dy, w, geom, residual=None, mask=None, out=None, bn=None, mask_bn
 
 
 # conv_x6hw.hip: the halo-staged X6 WGRAD (stride-1 "same" convs, K % 64, C % 32, OW a power of
-# two >= 8). It beats conv_f32.hip on images >= 16 wide (8 clients, c64 / c128: 0.49 / 0.46 ms vs
-# 0.65 / 0.50 ms) and loses on 8x8 (c256: 0.55 vs 0.50 ms: the halo is 60 % padding there),
-# profiles/x6hw_wgrad_r4.txt. DDL_F32_HALO_WGRAD=0 disables it; HW_MIN_W is the width rule.
+# two in 4..64). Which engine a geometry takes is measured where it can be: an 'x6hw:' entry of
+# f32_plans.json (scripts/halo_plan_probe.py writes one only where the halo kernel beat conv_f32.hip's
+# tuned plan in the same session) selects the halo kernel and its slice count. A geometry without an
+# entry keeps the width rule (HW_MIN_W: images >= 16 wide). DDL_F32_HALO_WGRAD=0 disables the kernel;
+# DDL_F32_HW_MIN_W, when set, is the only rule (A/B runs: 0 = every geometry the kernel takes).
 HALO_WGRAD = [os.environ.get("DDL_F32_HALO_WGRAD", "1") != "0"]
 HW_MIN_W = int(os.environ.get("DDL_F32_HW_MIN_W", "16"))
+HW_MIN_W_PINNED = "DDL_F32_HW_MIN_W" in os.environ
 HW_TARGET_WG = int(os.environ.get("DDL_F32_HW_TARGET_WG", "256"))  # one workgroup per CU (LDS-bound)
+HW_MIN_TILES = 3  # 128-pixel units (ddl_x6hw_tiles: pairs of 64-pixel tiles) a planner-chosen slice keeps
+
+
+def _hw_entry(geom):
+    """The measured 'x6hw:' plan of this geometry ([slices]) or None."""
+    _tuned(F_WGRAD, geom)  # loads the table
+    return _TUNED.get(f"x6hw:wgrad:{geom.G},{geom.N},{geom.H},{geom.W},{geom.C},{geom.K},{geom.R},{geom.S},"
+                      f"{geom.stride},{geom.pad}")
+
+
+def _hw_takes(a, geom) -> bool:
+    if not (HALO_WGRAD[0] and _MATH[0] != "mfma32"):
+        return False
+    if geom.W < HW_MIN_W and (HW_MIN_W_PINNED or _hw_entry(geom) is None):
+        return False
+    return bool(_lib.kernels().ddl_x6hw_ok(ctypes.byref(a)))
 
 
 def uses_halo_wgrad(geom) -> bool:
     """Does conv_wgrad take the halo WGRAD (conv_x6hw.hip) for this geometry?"""
-    a = _args(geom)
-    return HALO_WGRAD[0] and _MATH[0] != "mfma32" and geom.W >= HW_MIN_W \
-        and bool(_lib.kernels().ddl_x6hw_ok(ctypes.byref(a)))
+    return _hw_takes(_args(geom), geom)
 
 
 def _halo_wgrad(a, geom, device, split_k: int, ws_role: str) -> bool:
     """Launch the halo WGRAD when it takes this geometry: a measured slice count ('x6hw:' entries of
     f32_plans.json, scripts/halo_plan_probe.py), else split-K over pixel tiles until ~one
-    workgroup per CU (each slice keeping >= 3 tiles); slices folded in slice order."""
-    if not (HALO_WGRAD[0] and _MATH[0] != "mfma32") or geom.W < HW_MIN_W \
-            or not _lib.kernels().ddl_x6hw_ok(ctypes.byref(a)):
+    workgroup per CU (each slice keeping >= HW_MIN_TILES tiles); slices folded in slice order."""
+    if not _hw_takes(a, geom):
         return False
     lib = _lib.kernels()
     ntile = int(lib.ddl_x6hw_tiles(ctypes.byref(a)))
     base = (geom.K // 64) * (geom.C // 32) * geom.G
     split = split_k or 1
     if not split_k and TARGET_WG != 1:
-        _tuned(F_WGRAD, geom)  # loads the table
-        p = _TUNED.get(f"x6hw:wgrad:{geom.G},{geom.N},{geom.H},{geom.W},{geom.C},{geom.K},{geom.R},{geom.S},"
-                       f"{geom.stride},{geom.pad}")
+        p = _hw_entry(geom)
         if p is not None:
             split_k = split = int(p[0])
     if not split_k:
         target = min(HW_TARGET_WG, TARGET_WG)  # TARGET_WG = 1 pins split-K off for every conv
-        while base * split < target and ntile >= split * 2 * 3 and split < 128:
+        while base * split < target and ntile >= split * 2 * HW_MIN_TILES and split < 128:
             split *= 2
     n = geom.K * geom.R * geom.S * geom.C
     if split > 1:

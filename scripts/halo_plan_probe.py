@@ -1,6 +1,7 @@
 """Halo-kernel plan sweep (BP x split-K) per ResNet-18 stride-1 3x3 layer and client count, in
 one process: device time of FWD (with BN statistics) and DGRAD per pinned plan, against the
-default plan (functional_f32._halo_plan).
+default plan (functional_f32._halo_plan); and the WGRAD's engine (conv_f32.hip's tuned plan
+against the halo WGRAD at each slice count: an 'x6hw:' entry only where the halo kernel wins).
 
     python scripts/halo_plan_probe.py [--G 1 2 4 8] [--reps 20] [--out gpurun_out/x6h_plans.json]
 """
@@ -38,6 +39,41 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def wgrad_engines(name, g, x, w, dy, reps, plans, report):
+    """Stride-1 WGRAD of one geometry, both engines in this process: conv_f32.hip on its tuned plan
+    against the halo WGRAD (conv_x6hw.hip) at every candidate slice count. An 'x6hw:' entry (the
+    slice count) is written only where the halo kernel wins: functional_f32 takes the halo kernel
+    for the geometries that have one (and, without an entry, for images >= 16 wide)."""
+    old = F32.HALO_WGRAD[0], F32.HW_MIN_W
+    try:
+        F32.HW_MIN_W = 0  # every geometry the kernel takes
+        if not (old[0] and F32.uses_halo_wgrad(g)):
+            return
+        dw = torch.zeros_like(w)
+        base = (g.K // 64) * (g.C // 32) * g.G
+        F32.HALO_WGRAD[0] = False
+        t_old = timed(lambda: F32.conv_wgrad(dy, x, g, dw), reps)
+        F32.HALO_WGRAD[0] = True
+        res = []
+        for split in (1, 2, 4, 8, 16, 32, 64, 128):
+            if base * split > 2048:
+                break
+            res.append((timed(lambda: F32.conv_wgrad(dy, x, g, dw, split_k=split), reps), split))
+        res.sort()
+        key = f"x6hw:wgrad:{g.G},{g.N},{g.H},{g.W},{g.C},{g.K},{g.R},{g.S},{g.stride},{g.pad}"
+        wins = res[0][0] < t_old
+        if wins:
+            plans[key] = [res[0][1]]
+        report.append(dict(G=g.G, layer=name, mode="wgrad", conv_f32_us=round(t_old * 1e3, 1),
+                           halo_best=[res[0][1]], halo_best_us=round(res[0][0] * 1e3, 1),
+                           engine="x6hw" if wins else "conv_f32"))
+        print(f"G={g.G} {name} wgrad: conv_f32 {t_old * 1e3:6.1f} us | halo best split={res[0][1]} "
+              f"{res[0][0] * 1e3:6.1f} us -> {'x6hw' if wins else 'conv_f32 (no entry)'} | "
+              + " ".join(f"{s_}:{t * 1e3:.1f}" for t, s_ in res), flush=True)
+    finally:
+        F32.HALO_WGRAD[0], F32.HW_MIN_W = old
+
+
 LAYERS = {"c64": (32, 64), "c128": (16, 128), "c256": (8, 256), "c512": (4, 512)}
 
 
@@ -47,7 +83,8 @@ def main():
     ap.add_argument("--N", type=int, default=100)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--model", default="resnet18", choices=("resnet18", "resnet50", "resnet50_flat1x1"))
-    ap.add_argument("--out", default="", help="write the best plans as 'x6h:' table entries (scripts/merge_plans.py)")
+    ap.add_argument("--out", default="", help="write the best plans as 'x6h:' / 'x6hw:' table entries (scripts/merge_plans.py)")
+    ap.add_argument("--wgrad-only", action="store_true", help="skip the FWD / DGRAD plan sweep")
     a = ap.parse_args()
     plans, report = {}, []
     dev = torch.device("cuda")
@@ -67,7 +104,7 @@ def main():
             x = torch.randn(g.G, g.N, g.H, g.W, g.C, device=dev)
             w = torch.randn(g.G, g.K, g.R, g.S, g.C, device=dev) * 0.05
             dy = torch.randn(g.G, g.N, g.P, g.Q, g.K, device=dev)
-            for mode, mname in ((F32.F_FWD, "fwd"), (F32.F_DGRAD, "dgrad")):
+            for mode, mname in (() if a.wgrad_only else ((F32.F_FWD, "fwd"), (F32.F_DGRAD, "dgrad"))):
                 run = (lambda: F32.conv_fwd(x, w, g, stats=F32.SlotStats())) if mode == F32.F_FWD else \
                     (lambda: F32.conv_dgrad(dy, w, g))
                 F32.clear_plan(mode, g)
@@ -94,23 +131,8 @@ def main():
                                    best=plans[key], best_us=round(best[0] * 1e3, 1)))
                 print(f"G={G} {name} {mname}: default {dflt} {t0 * 1e3:6.1f} us | best bp={best[1]} split={best[2]} "
                       f"{best[0] * 1e3:6.1f} us | " + " ".join(f"{b}/{s}:{t * 1e3:.1f}" for t, b, s in res), flush=True)
-            if a.model != "resnet50_flat1x1" and F32.uses_halo_wgrad(g):  # halo WGRAD: slice count sweep
-                dw = torch.zeros_like(w)
-                base = (g.K // 64) * (g.C // 32) * G
-                t0 = timed(lambda: F32.conv_wgrad(dy, x, g, dw), a.reps)
-                res = []
-                for split in (1, 2, 4, 8, 16, 32, 64, 128):
-                    if base * split > 2048:
-                        break
-                    res.append((timed(lambda: F32.conv_wgrad(dy, x, g, dw, split_k=split), a.reps), split))
-                res.sort()
-                key = f"x6hw:wgrad:{g.G},{g.N},{g.H},{g.W},{g.C},{g.K},{g.R},{g.S},{g.stride},{g.pad}"
-                plans[key] = [res[0][1]]
-                report.append(dict(G=G, layer=name, mode="wgrad", default_us=round(t0 * 1e3, 1),
-                                   best=plans[key], best_us=round(res[0][0] * 1e3, 1)))
-                print(f"G={G} {name} wgrad(x6hw): default {t0 * 1e3:6.1f} us | best split={res[0][1]} "
-                      f"{res[0][0] * 1e3:6.1f} us | " + " ".join(f"{s_}:{t * 1e3:.1f}" for t, s_ in res), flush=True)
-                del dw
+            if a.model != "resnet50_flat1x1":  # WGRAD: engine and slice count
+                wgrad_engines(name, g, x, w, dy, a.reps, plans, report)
             del x, w, dy
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
