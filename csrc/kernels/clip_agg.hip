@@ -1,0 +1,246 @@
+// Clipped FedAvg aggregation: the norm-bounding defence (Sun et al. 2019) and DP-FedAvg
+// (McMahan et al. 2018) [north-star, absent in reference]. Each client update u_k = x_k - c is
+// scaled to L2 norm at most C before the weighted mean; DP-FedAvg adds N(0, std^2) to the result.
+//
+//   ddl_update_sqnorm : sq[k] = sum_i fl32(x_ki - c_i)^2, squares accumulated in double
+//   ddl_clip_scales   : norms[k] = sqrt(sq[k]), cs[k] = coeff[k] * min(1, C / norms[k]);
+//                       cs[k] = 0 for a row whose squared norm is NaN / Inf
+//   ddl_clipped_sum   : delta[i] (+)= sum_k cs[k] * fl32(x_ki - c_i), rows with cs[k] == 0 not read
+//   ddl_apply_update  : w[i] = c[i] + delta[i] + std * z_i, z_i ~ N(0, 1) from Philox
+//
+// All four stream: two reads of the client rows (norms, then the sum), 16-B loads where every row
+// start is 16-B aligned (the scalar path otherwise, as weighted_sum_kernel), no LDS tiling, no
+// scratch, no float atomics, and no block waits for another: the per-block partial squared norms
+// go out with plain stores and a tiny second launch folds them in a fixed order, so the norms (and
+// with them the whole aggregate) are bit-reproducible. G is bounded by memory only.
+#include "ddl_common.h"
+
+// blocks along a row for the squared norms: about 2048 blocks in all over the G rows (256 CUs x 8
+// resident blocks, the rest by the grid-stride loop). Measured at 8 rows x 11.2M with a centre:
+// 0.068 ms at 256 blocks per row, 0.095 at 1024, 0.101 at 2048 and 8192 -- every block ends in a
+// reduction and a barrier, so few long blocks beat many short ones.
+static int sqnorm_row_blocks(int G, long long n) {
+  const int bx = grid_for((n + 3) / 4, 256);
+  const int lim = G >= 2048 ? 1 : 2048 / (G < 1 ? 1 : G);
+  return bx < lim ? bx : lim;
+}
+
+__global__ __launch_bounds__(256) void update_sqnorm_kernel(const float* __restrict__ X, long long ld,
+                                                            const float* __restrict__ c, int G, long long n,
+                                                            double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double red[4];
+  // float4 path only when every row start and the centre are 16-B aligned
+  const bool vec = (ld % 4) == 0 && (((uintptr_t)X | (uintptr_t)c) & 15) == 0;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int g = blockIdx.y; g < G; g += gridDim.y) {
+    const float* row = X + (long long)g * ld;
+    // the difference rounded to fp32 (the update as `rows - w_global` forms it), its square exact
+    // in double and added in double from the first add
+    double acc = 0.0;
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
+         t += (long long)gridDim.x * blockDim.x) {
+      const long long e = t * 4;
+      if (e + 4 <= n && vec) {
+        const float4 v = *(const float4*)(row + e);
+        const float4 m = c ? *(const float4*)(c + e) : make_float4(0, 0, 0, 0);
+        const float d0 = v.x - m.x, d1 = v.y - m.y, d2 = v.z - m.z, d3 = v.w - m.w;
+        acc += (double)d0 * (double)d0;
+        acc += (double)d1 * (double)d1;
+        acc += (double)d2 * (double)d2;
+        acc += (double)d3 * (double)d3;
+      } else {
+        for (long long k = e; k < min(n, e + 4); ++k) {
+          const float d = row[k] - (c ? c[k] : 0.f);
+          acc += (double)d * (double)d;
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) red[wid] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long long)g * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();  // red is reused by the block's next row
+  }
+}
+
+// sq[g] = the row's bx partials: thread t adds partials t, t + 256, ... in order, then a fixed LDS
+// tree (the order depends on bx alone)
+__global__ __launch_bounds__(256) void sqnorm_fold_kernel(const double* __restrict__ part, int bx, int G,
+                                                          double* __restrict__ sq) {
+  __shared__ double red[256];
+  for (int g = blockIdx.x; g < G; g += gridDim.x) {
+    const double* p = part + (long long)g * bx;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < bx; b += 256) s += p[b];
+    red[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+      if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) sq[g] = red[0];
+    __syncthreads();
+  }
+}
+
+// doubles of scratch `ddl_update_sqnorm` needs for G rows of n coordinates
+DDL_API long long ddl_update_sqnorm_workspace(int G, long long n) {
+  if (G < 1 || n < 1) return 0;
+  return (long long)G * sqnorm_row_blocks(G, n);
+}
+
+DDL_API int ddl_update_sqnorm(const float* X, long long ld, const float* center, int G, long long n,
+                              double* part, long long part_cap, double* sq, hipStream_t s) {
+  if (G < 1 || n < 1 || part_cap < ddl_update_sqnorm_workspace(G, n)) return (int)hipErrorInvalidValue;
+  const int bx = sqnorm_row_blocks(G, n);
+  const int gy = G < 65535 ? G : 65535;
+  // one block per row: its partial is the row's squared norm
+  hipLaunchKernelGGL(update_sqnorm_kernel, dim3(bx, gy), dim3(256), 0, s, X, ld, center, G, n,
+                     bx == 1 ? sq : part);
+  if (bx > 1)
+    hipLaunchKernelGGL(sqnorm_fold_kernel, dim3(gy), dim3(256), 0, s, part, bx, G, sq);
+  return (int)hipGetLastError();
+}
+
+// norm_k = sqrt(sq_k) and s_k = min(1, C / norm_k) in double, s_k rounded to fp32 (exactly 1 for
+// norm_k <= C, norm_k = 0 included), cs_k = fl32(coeff_k * s_k). A squared norm that is NaN / Inf
+// (a NaN / Inf entry in the row) gives cs_k = 0, which the sum kernel takes as "skip the row".
+__global__ void clip_scales_kernel(const double* __restrict__ sq, const float* __restrict__ coeff, int G,
+                                   double clip, float* __restrict__ norms, float* __restrict__ cs) {
+#pragma clang fp contract(off)
+  GSTRIDE_LOOP(k, G) {
+    const double q = sq[k];
+    const double nrm = sqrt(q);
+    norms[k] = (float)nrm;  // +inf for a finite row too long for fp32
+    float r = 0.f;
+    if (q < (double)INFINITY) {  // false for NaN and +inf
+      const float sc = (nrm <= clip) ? 1.f : (float)(clip / nrm);
+      r = coeff[k] * sc;
+    }
+    cs[k] = r;
+  }
+}
+
+DDL_API int ddl_clip_scales(const double* sq, const float* coeff, int G, double clip, float* norms,
+                            float* cs, hipStream_t s) {
+  if (G < 1 || !(clip > 0.0)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(clip_scales_kernel, dim3(grid_for(G, 256)), dim3(256), 0, s, sq, coeff, G, clip,
+                     norms, cs);
+  return (int)hipGetLastError();
+}
+
+__global__ void clipped_sum_kernel(const float* __restrict__ X, long long ld, const float* c,
+                                   const float* __restrict__ cs, int G, long long n, float* out,
+                                   int accumulate) {
+  // difference, product and sum each rounded on their own (no fused multiply-add), rows added in
+  // order: the same bits wherever the rows live, as weighted_sum_kernel
+#pragma clang fp contract(off)
+  const bool vec = (ld % 4) == 0 && (((uintptr_t)out | (uintptr_t)X | (uintptr_t)c) & 15) == 0;
+  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
+       t += (long long)gridDim.x * blockDim.x) {
+    const long long e = t * 4;
+    if (e + 4 <= n && vec) {
+      float4 acc = accumulate ? *(const float4*)(out + e) : make_float4(0, 0, 0, 0);
+      const float4 m = c ? *(const float4*)(c + e) : make_float4(0, 0, 0, 0);
+      for (int g = 0; g < G; ++g) {
+        const float k = cs[g];
+        if (k == 0.f) continue;  // dropped row (or zero weight): not read, 0 * NaN would be NaN
+        const float4 v = *(const float4*)(X + g * ld + e);
+        acc.x = acc.x + k * (v.x - m.x); acc.y = acc.y + k * (v.y - m.y);
+        acc.z = acc.z + k * (v.z - m.z); acc.w = acc.w + k * (v.w - m.w);
+      }
+      *(float4*)(out + e) = acc;
+    } else {
+      for (long long j = e; j < min(n, e + 4); ++j) {
+        float acc = accumulate ? out[j] : 0.f;
+        const float m = c ? c[j] : 0.f;
+        for (int g = 0; g < G; ++g) {
+          const float k = cs[g];
+          if (k == 0.f) continue;
+          acc = acc + k * (X[g * ld + j] - m);
+        }
+        out[j] = acc;
+      }
+    }
+  }
+}
+
+DDL_API int ddl_clipped_sum(const float* X, long long ld, const float* center, const float* cs, int G,
+                            long long n, float* out, int accumulate, hipStream_t s) {
+  if (G < 0 || n < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(clipped_sum_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, X, ld,
+                     center, cs, G, n, out, accumulate);
+  return (int)hipGetLastError();
+}
+
+// Gaussian noise of the server update: z_i is a pure function of (seed, round, global index i).
+// Philox key (seed_lo, seed_hi), counter (q_lo, q_hi, TAG, round) with q = i >> 2, and the four
+// words r give two Box-Muller pairs: z[4q] = R(r.x) cos(2 pi U(r.y)), z[4q+1] = R(r.x) sin(..),
+// z[4q+2] = R(r.z) cos(2 pi U(r.w)), z[4q+3] = R(r.z) sin(..), U = u32_to_unit in (0, 1] and
+// R(x) = sqrt(-2 ln U(x)) <= 5.77. The precise logf / sincosf: the pass moves 3n floats, the math
+// is free, and the tail of the noise should not depend on an approximate log.
+constexpr uint32_t CLIP_NOISE_TAG = 0x3c6ef372u;
+
+__device__ __forceinline__ void normal4(uint2 key, long long q, uint32_t round, float (&z)[4]) {
+  const uint4 r = philox4x32(make_uint4((uint32_t)q, (uint32_t)((unsigned long long)q >> 32), CLIP_NOISE_TAG, round), key);
+  const float r0 = sqrtf(-2.0f * logf(u32_to_unit(r.x)));
+  const float r1 = sqrtf(-2.0f * logf(u32_to_unit(r.z)));
+  float s0, c0, s1, c1;
+  sincosf(6.2831853071795864769f * u32_to_unit(r.y), &s0, &c0);
+  sincosf(6.2831853071795864769f * u32_to_unit(r.w), &s1, &c1);
+  z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
+}
+
+// w[j] = (c[j] or 0) + delta[j] + std * z[off + j], j in [0, n). One thread per quad q of the
+// GLOBAL index off + j, so a call on a sub-slice draws what the full call draws; `off` need not be a
+// multiple of 4 (then the scalar path). w may alias c: every thread reads its elements before it
+// writes them. std == 0: exactly c + delta, no RNG work.
+__global__ void apply_update_kernel(float* w, const float* c, const float* __restrict__ delta, long long n,
+                                    long long off, float std, uint2 key, uint32_t round) {
+#pragma clang fp contract(off)
+  const long long q0 = off >> 2;
+  const long long nq = ((off + n + 3) >> 2) - q0;
+  const bool vec = (off & 3) == 0 && (((uintptr_t)w | (uintptr_t)c | (uintptr_t)delta) & 15) == 0;
+  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < nq;
+       t += (long long)gridDim.x * blockDim.x) {
+    const long long q = q0 + t;
+    const long long j0 = q * 4 - off;  // local index of the quad's first element (may be < 0)
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (std != 0.f) normal4(key, q, round, z);
+    if (vec && j0 + 4 <= n) {
+      const float4 d = *(const float4*)(delta + j0);
+      float4 o = d;
+      if (c) {
+        const float4 m = *(const float4*)(c + j0);
+        o.x = m.x + d.x; o.y = m.y + d.y; o.z = m.z + d.z; o.w = m.w + d.w;
+      }
+      if (std != 0.f) {
+        o.x = o.x + std * z[0]; o.y = o.y + std * z[1];
+        o.z = o.z + std * z[2]; o.w = o.w + std * z[3];
+      }
+      *(float4*)(w + j0) = o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const long long j = j0 + e;
+        if (j >= 0 && j < n) {
+          float o = c ? c[j] + delta[j] : delta[j];
+          if (std != 0.f) o = o + std * z[e];
+          w[j] = o;
+        }
+      }
+    }
+  }
+}
+
+DDL_API int ddl_apply_update(float* w, const float* center, const float* delta, long long n, long long off,
+                             float std, unsigned long long seed, unsigned int round, hipStream_t s) {
+  if (n < 1 || off < 0) return (int)hipErrorInvalidValue;
+  const long long nq = ((off + n + 3) >> 2) - (off >> 2);
+  hipLaunchKernelGGL(apply_update_kernel, dim3(grid_for(nq, 256)), dim3(256), 0, s, w, center, delta, n,
+                     off, std, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), (uint32_t)round);
+  return (int)hipGetLastError();
+}

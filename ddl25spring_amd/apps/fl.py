@@ -23,9 +23,13 @@ class FLConfig:
     rounds: int = 10
     iid: bool = True
     seed: int = 10
-    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum
+    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped
     trim: float = 0.1
     krum_f: int = 1
+    clip_norm: float = 1.0         # clipped: L2 bound C on every client update
+    noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
+    agg_weighting: str = "samples"  # clipped: samples (n_k / n) | uniform (1 / K)
+    dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
     attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider
     malicious: int = 0             # number of malicious clients (ids 0..malicious-1)
     dropout: float = 0.0
@@ -53,7 +57,9 @@ def build_server(cfg: FLConfig, ctx):
     algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight}[cfg.algorithm]
     kw = dict(lr=cfg.lr, client_fraction=cfg.client_fraction, seed=cfg.seed,
               test_data=DeviceImageDataset(test, ctx.device), aggregator=cfg.aggregator,
-              agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f}, attack=attack, ctx=ctx,
+              agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": cfg.clip_norm,
+                          "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
+                          "weighting": cfg.agg_weighting}, attack=attack, ctx=ctx,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
               straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline)
     if algo is FedAvg:
@@ -63,8 +69,10 @@ def build_server(cfg: FLConfig, ctx):
 
 def run_fl(cfg: FLConfig, ctx, log=print):
     from ..fl import checkpoint as ckpt
+    from ..fl import privacy
     from ..utils.metrics import JsonlLogger
     server = build_server(cfg, ctx)
+    noisy = cfg.noise_multiplier > 0 and getattr(server.aggregator, "takes_center", False)
     if cfg.checkpoint:
         res = ckpt.run_with_checkpoints(server, cfg.rounds, cfg.checkpoint)
     else:
@@ -78,6 +86,8 @@ def run_fl(cfg: FLConfig, ctx, log=print):
                            samples_per_s=res.samples[i] / max(res.round_time[i], 1e-9))
             if i < len(res.phase_ms):
                 rec["phase_ms"] = res.phase_ms[i]
+            if noisy:  # (epsilon, dp_delta)-DP spent after this round (fl/privacy.py, q = K / N)
+                rec["epsilon"] = privacy.epsilon(i + 1, server.K / server.N, cfg.noise_multiplier, cfg.dp_delta)
             jl.log(**rec)
     if log and ctx.rank == 0:
         log(res.as_df(with_throughput=True).to_string(index=False))

@@ -17,6 +17,9 @@
   scores and selects redundantly on every GPU in one small kernel (krum_select) and averages the
   winners' shards by index (mean_rows_idx). One GPU skips the sharding: the rules read the client
   rows in place; several GPUs build the all-to-all send buffer with one pack kernel.
+* ``ClippedMean`` — norm bounding (Sun et al. 2019) and DP-FedAvg (McMahan et al. 2018)
+  [north-star]: each update clipped to L2 norm C, then the weighted mean, optionally plus Gaussian
+  noise; streaming kernels (clip_agg.hip), the mean's cross-rank route, any number of clients.
 Robust rules operate on client *updates* (w_k - w_global) — distances between raw weights would
 cancel catastrophically in fp32.
 """
@@ -44,6 +47,10 @@ class MeanAggregator:
             out.zero_()
         else:
             Fn.weighted_sum(rows, coeffs, out)
+        return self.cross_rank_sum(ctx, out)
+
+    def cross_rank_sum(self, ctx, out: torch.Tensor):
+        """out[P] (this rank's partial) -> the sum over the ranks, in place, on every rank."""
         if not ctx.is_distributed:
             return out
         if not self.ordered:
@@ -71,6 +78,99 @@ class MeanAggregator:
         if getattr(ctx, "ipc", None) is not None:
             return "ipc peer-read rank-ordered sum"
         return "rank-ordered all-gather + sum"
+
+
+class ClippedMean(MeanAggregator):
+    """Norm-bounded FedAvg (Sun et al. 2019) and DP-FedAvg (McMahan et al. 2018) [north-star]:
+    every client update ``u_k = w_k - center`` is scaled to L2 norm at most ``clip`` before the
+    weighted mean, and ``noise_multiplier`` z > 0 adds N(0, (z * clip / K_r)^2) to the aggregate.
+
+    Per GPU: update_sqnorm -> clip_scales -> clipped_sum into a cached ``delta [P]`` (two reads of
+    the client rows, no all-to-all, no limit on K); ``delta`` then takes ``MeanAggregator``'s route
+    across the ranks; apply_update writes ``out = center + delta + noise`` with the identical noise
+    on every rank (a pure function of seed, round and coordinate). A row holding a NaN / Inf entry
+    is dropped (weight 0). No host synchronisation, except in ``last_norms``.
+
+    ``weighting``: "samples" keeps the server's n_k / n; "uniform" weighs every reporting client
+    1 / K_r (K_r = sum(counts), the same on every rank). Noise needs "uniform": the sensitivity of
+    a sample-weighted sum to one client is not clip / K_r."""
+    name = "clipped_mean"
+    needs_all = False
+    takes_center = True
+
+    def __init__(self, clip: float, noise_multiplier: float = 0.0, seed: int = 0,
+                 weighting: str = "samples", ordered: bool | None = None):
+        super().__init__(ordered)
+        self.clip, self.noise_multiplier, self.seed = float(clip), float(noise_multiplier), int(seed)
+        if not self.clip > 0.0:
+            raise ValueError(f"clip must be positive, got {clip}")
+        if weighting not in ("samples", "uniform"):
+            raise ValueError(f"weighting must be 'samples' or 'uniform', got {weighting!r}")
+        if self.noise_multiplier < 0.0:
+            raise ValueError(f"noise_multiplier must be >= 0, got {noise_multiplier}")
+        if self.noise_multiplier > 0.0 and weighting != "uniform":
+            raise ValueError("noise_multiplier > 0 needs weighting='uniform': the sensitivity of a "
+                             "sample-weighted sum is not clip / K")
+        self.weighting = weighting
+        self.rounds = 0      # the noise stream's round: this aggregator's own call counter
+        self.last_k = 0      # clients that reported in the last round (all ranks)
+        self._delta: dict = {}
+        self._uniform: dict = {}
+        self._norms = None
+
+    def __call__(self, ctx, rows: torch.Tensor, coeffs: torch.Tensor, out: torch.Tensor,
+                 center: torch.Tensor | None = None, counts: list[int] | None = None):
+        """rows [G_local, P], coeffs [G_local], center [P] or None (the rows are the updates) ->
+        out[P] = center + sum_k c_k * clip(rows_k - center) (+ noise); out may be center."""
+        G, P = rows.shape
+        if counts is None:
+            if ctx.is_distributed and self.weighting == "uniform":
+                raise ValueError("uniform weighting over several ranks needs the per-rank client counts")
+            counts = [G]
+        K_r = int(sum(counts))
+        dev = out.device
+        delta = self._delta.get((P, dev))
+        if delta is None:
+            delta = self._delta[(P, dev)] = torch.empty(P, dtype=torch.float32, device=dev)
+        if G == 0:
+            delta.zero_()
+            self._norms = None
+        else:
+            if rows.stride(1) != 1:
+                rows = rows.contiguous()
+            if self.weighting == "uniform":
+                coeffs = self._uniform.get((G, K_r, dev))
+                if coeffs is None:
+                    coeffs = self._uniform[(G, K_r, dev)] = torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev)
+            sq = Fn.update_sqnorm(rows, center)
+            self._norms, cs = Fn.clip_scales(sq, coeffs, self.clip)
+            Fn.clipped_sum(rows, center, cs, delta)
+        self.cross_rank_sum(ctx, delta)
+        std = self.noise_multiplier * self.clip / K_r if K_r else 0.0
+        Fn.apply_update(out, center, delta, std, self.seed, self.rounds)
+        self.rounds += 1
+        self.last_k = K_r
+        return out
+
+    @property
+    def last_norms(self) -> list[float]:
+        """L2 norms of this rank's client updates in the last round, before clipping (syncs the
+        device). +inf / nan mark a row that was dropped or too long for fp32."""
+        return [] if self._norms is None else self._norms.tolist()
+
+    def epsilon(self, N: int, delta: float) -> float:
+        """(epsilon, delta)-DP spent so far on a population of N clients: q = K_r / N, the rounds
+        aggregated so far, RDP accountant of ``fl/privacy.py`` (infinite without noise)."""
+        from . import privacy
+        if self.noise_multiplier <= 0.0:
+            return math.inf
+        return privacy.epsilon(self.rounds, min(1.0, self.last_k / N), self.noise_multiplier, delta)
+
+    def state_dict(self) -> dict:
+        return {"rounds": self.rounds, "last_k": self.last_k}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.rounds, self.last_k = int(sd["rounds"]), int(sd.get("last_k", 0))
 
 
 class _Sharded:
@@ -185,4 +285,7 @@ def make_aggregator(name: str, **kw):
         return Krum(kw.get("f", 1), 1)
     if name in ("multikrum", "multi_krum"):
         return Krum(kw.get("f", 1), kw.get("m", 2))
+    if name in ("clipped", "clipped_mean", "norm_clip"):
+        return ClippedMean(kw.get("clip", 1.0), kw.get("noise_multiplier", 0.0), kw.get("seed", 0),
+                           kw.get("weighting", "samples"))
     raise ValueError(f"unknown aggregator {name}")

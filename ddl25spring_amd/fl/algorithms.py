@@ -130,6 +130,8 @@ class FederatedBase:
                 sd[name] = getattr(self, name).detach().cpu().clone()
         if self.attack is not None:
             sd["attack"] = self.attack.state_dict()
+        if hasattr(self.aggregator, "state_dict"):  # e.g. ClippedMean's noise round counter
+            sd["aggregator"] = self.aggregator.state_dict()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -155,6 +157,8 @@ class FederatedBase:
             self.sim_time = list(sd["sim_time"])
         if self.attack is not None and "attack" in sd:
             self.attack.load_state_dict(sd["attack"])
+        if "aggregator" in sd and hasattr(self.aggregator, "load_state_dict"):
+            self.aggregator.load_state_dict(sd["aggregator"])
 
     # ------------------------------------------------------------------ helpers
     def _assign(self, chosen):
@@ -295,7 +299,10 @@ class FedAvg(FederatedBase):
         return dt, samples
 
     def _aggregate(self, rows, coeffs, counts):
-        if not getattr(self.aggregator, "needs_all", False):
+        if getattr(self.aggregator, "takes_center", False):
+            # clipped mean: updates against w_global, clipped, averaged and added back in place
+            self.aggregator(self.ctx, rows, coeffs, self.w_global, center=self.w_global, counts=counts)
+        elif not getattr(self.aggregator, "needs_all", False):
             self.aggregator(self.ctx, rows, coeffs, self.w_global)
         else:
             upd = rows - self.w_global  # robust rules act on updates
@@ -350,7 +357,9 @@ class FedSGD(FederatedBase):
             self.attack.poison_updates(st.grad[:G], torch.zeros_like(self.w_global), mine)
         coeffs = torch.tensor([self.counts[c] / total for c in mine], dtype=torch.float32,
                               device=self.dev)
-        if not getattr(self.aggregator, "needs_all", False):
+        if getattr(self.aggregator, "takes_center", False):  # the updates are the gradients
+            self.aggregator(self.ctx, st.grad[:G], coeffs, self.g_global, center=None, counts=counts)
+        elif not getattr(self.aggregator, "needs_all", False):
             self.aggregator(self.ctx, st.grad[:G], coeffs, self.g_global)
         else:
             self.g_global.copy_(self.aggregator(self.ctx, st.grad[:G], counts, self.w_global.numel(),

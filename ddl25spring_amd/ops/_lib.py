@@ -31,6 +31,8 @@ i32 = ctypes.c_int
 i64 = ctypes.c_longlong
 u64 = ctypes.c_ulonglong
 f32 = ctypes.c_float
+f64 = ctypes.c_double
+u32 = ctypes.c_uint
 fp = ctypes.POINTER(ctypes.c_float)
 
 
@@ -168,6 +170,12 @@ _SIGS = {
     "ddl_pack_shards": [vp, i64, i32, i64, i32, i64, i32, vp, vp],
     "ddl_krum_select": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ddl_mean_rows_idx": [vp, i64, vp, i32, i64, vp, vp],
+    # clip_agg.hip
+    "ddl_update_sqnorm_workspace": [i32, i64],
+    "ddl_update_sqnorm": [vp, i64, vp, i32, i64, vp, i64, vp, vp],
+    "ddl_clip_scales": [vp, vp, i32, f64, vp, vp, vp],
+    "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
+    "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
 }
 
 # fp32-activation twins of the templated memory-bound launchers (nn_ops.hip): same signatures
@@ -210,7 +218,7 @@ _SIGS.update({
 })
 _RESTYPES = {"ddl_convf32_slots": ctypes.c_longlong, "ddl_convf32_workspace": ctypes.c_longlong,
              "ddl_x6h_workspace": ctypes.c_longlong, "ddl_x6h_slots": ctypes.c_longlong, "ddl_bnf_fold_ws": ctypes.c_longlong, "ddl_bnf_fold_tickets": ctypes.c_longlong,
-             "ddl_gram_f32_workspace": ctypes.c_longlong}
+             "ddl_gram_f32_workspace": ctypes.c_longlong, "ddl_update_sqnorm_workspace": ctypes.c_longlong}
 
 _OPTIONAL_SIGS: dict[str, list] = {}
 

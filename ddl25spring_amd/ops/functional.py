@@ -1475,3 +1475,89 @@ def coord_select(X, mode: str, trim: int = 0):
     check(_lib.kernels().ddl_coord_select(ptr(X), X.stride(0), X.shape[0], X.shape[1], m, trim,
                                           ptr(out), stream()), "coord_select")
     return out
+
+
+# ---------------------------------------------------------------- clipped aggregation (clip_agg.hip)
+def update_sqnorm(rows, center=None):
+    """sq[k] = sum_i fl32(rows[k, i] - center[i])^2 -> float64 [G]: the difference rounded to fp32
+    (as ``rows - w_global`` forms an update), the squares accumulated in double. Rows may be strided
+    views with any alignment; per-block partials are folded in a fixed order (bit-reproducible)."""
+    if not rows.is_cuda:
+        return ref.update_sqnorm(rows, center)
+    G, n = rows.shape
+    assert rows.dtype == torch.float32 and (G == 0 or rows.stride(1) == 1)
+    assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == n)
+    sq = torch.zeros(G, dtype=torch.float64, device=rows.device)
+    if G == 0 or n == 0:
+        return sq
+    cap = _lib.kernels().ddl_update_sqnorm_workspace(G, n)
+    part = torch.empty(cap, dtype=torch.float64, device=rows.device)
+    check(_lib.kernels().ddl_update_sqnorm(ptr(rows), rows.stride(0), ptr(center), G, n, ptr(part), cap,
+                                           ptr(sq), stream()), "update_sqnorm")
+    sq._keep = part  # the scratch must outlive the (asynchronous) launches
+    return sq
+
+
+def clip_scales(sq, coeff, clip: float):
+    """Squared update norms sq [G] (float64), weights coeff [G] -> (norms [G] fp32, cs [G] fp32):
+    norm_k = sqrt(sq_k), s_k = min(1, clip / norm_k) in double rounded to fp32 (exactly 1 for
+    norm_k <= clip), cs_k = coeff_k * s_k. A row whose squared norm is NaN / Inf gets cs_k = 0:
+    ``clipped_sum`` skips it. Nothing is copied to the host."""
+    clip = float(clip)
+    if not clip > 0.0:
+        raise ValueError(f"clip_scales: clip must be positive, got {clip}")
+    if not sq.is_cuda:
+        return ref.clip_scales(sq, coeff, clip)
+    G = sq.numel()
+    assert sq.dtype == torch.float64 and sq.is_contiguous() and coeff.numel() == G
+    norms = torch.empty(G, dtype=torch.float32, device=sq.device)
+    cs = torch.empty(G, dtype=torch.float32, device=sq.device)
+    if G:
+        coeff = coeff.float().contiguous()
+        check(_lib.kernels().ddl_clip_scales(ptr(sq), ptr(coeff), G, clip, ptr(norms), ptr(cs), stream()),
+              "clip_scales")
+        cs._keep = coeff
+    return norms, cs
+
+
+def clipped_sum(rows, center, cs, out, accumulate=False):
+    """out[i] (+)= sum_k cs[k] * fl32(rows[k, i] - center[i]) (center None: zero): every product
+    rounded on its own, added in row order; rows with cs[k] == 0 are not read."""
+    if not rows.is_cuda:
+        ref.clipped_sum(rows, center, cs, out, accumulate)
+        return out
+    G, n = rows.shape
+    assert rows.dtype == torch.float32 and (G == 0 or rows.stride(1) == 1)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n
+    assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == n)
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == G
+    if G == 0 or n == 0:
+        if not accumulate:
+            out.zero_()
+        return out
+    check(_lib.kernels().ddl_clipped_sum(ptr(rows), rows.stride(0), ptr(center), ptr(cs), G, n, ptr(out),
+                                         int(accumulate), stream()), "clipped_sum")
+    return out
+
+
+def apply_update(out, center, delta, std: float = 0.0, seed: int = 0, round: int = 0, offset: int = 0):
+    """out[j] = (center[j] or 0) + delta[j] + std * z[offset + j]; ``out`` may be ``center``.
+
+    z_i ~ N(0, 1) is a pure function of (seed, round, i): Philox-4x32-10 with key (seed_lo, seed_hi)
+    and counter (q_lo, q_hi, tag, round), q = i >> 2, two Box-Muller pairs per call (clip_agg.hip).
+    A call on the sub-slice [a, b) with ``offset=a`` draws what the full call draws there.
+    ``std == 0`` gives exactly center + delta."""
+    n = out.numel()
+    std, seed, round, offset = float(std), int(seed) & (2 ** 64 - 1), int(round) & 0xFFFFFFFF, int(offset)
+    if offset < 0:
+        raise ValueError("apply_update: offset must be >= 0")
+    if not out.is_cuda:
+        ref.apply_update(out, center, delta, std, seed, round, offset)
+        return out
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == n
+    assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == n)
+    if n:
+        check(_lib.kernels().ddl_apply_update(ptr(out), ptr(center), ptr(delta), n, offset, std, seed, round,
+                                              stream()), "apply_update")
+    return out

@@ -380,6 +380,76 @@ def coord_select(X, mode, trim=0):
     return s[trim:K - trim].mean(0)
 
 
+# ------------------------------------------------- clipped aggregation (clip_agg.hip), torch twins
+def update_sqnorm(rows, center=None):
+    d = rows if center is None else rows - center  # rounded to fp32, then squared in double
+    return d.double().square().sum(1)
+
+
+def clip_scales(sq, coeff, clip):
+    nrm = sq.double().sqrt()
+    one = torch.ones_like(nrm)
+    s = torch.where(nrm <= clip, one, clip / nrm).float()
+    cs = coeff.float() * s
+    cs = torch.where(torch.isfinite(sq), cs, torch.zeros_like(cs))  # NaN / Inf row: skipped
+    return nrm.float(), cs
+
+
+def clipped_sum(rows, center, cs, out, accumulate=False):
+    acc = out.clone() if accumulate else torch.zeros_like(out)
+    for k, c in enumerate(cs.tolist()):
+        if c == 0.0:
+            continue  # not read: 0 * NaN would be NaN
+        d = rows[k] if center is None else rows[k] - center
+        acc = acc + cs[k] * d  # product rounded, then added, in row order
+    out.copy_(acc)
+
+
+CLIP_NOISE_TAG = 0x3C6EF372
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo_t(a: int, b):
+    """(hi, lo) 32-bit words of a * b for a 32-bit constant a and an int64 tensor b < 2**32, in
+    int64 arithmetic (16-bit limbs of b: no product reaches 2**63)."""
+    p0, p1 = a * (b & 0xFFFF), a * (b >> 16)
+    t = p0 + ((p1 & 0xFFFF) << 16)
+    return (p1 >> 16) + (t >> 32), t & _M32
+
+
+def philox4x32_t(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox-4x32-10 (csrc/include/ddl_common.h) on int64 tensors holding 32-bit words."""
+    for _ in range(10):
+        hi0, lo0 = _mulhilo_t(0xD2511F53, c0)
+        hi1, lo1 = _mulhilo_t(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def update_noise(n: int, seed: int, round: int, offset: int = 0):
+    """z[offset : offset + n] of the N(0, 1) stream of (seed, round): apply_update_kernel's draws."""
+    q0 = offset >> 2
+    q = torch.arange(q0, ((offset + n + 3) >> 2), dtype=torch.int64)
+    zero = torch.zeros_like(q)
+    r = philox4x32_t(q & _M32, q >> 32, zero + CLIP_NOISE_TAG, zero + (round & _M32),
+                     seed & _M32, (seed >> 32) & _M32)
+    u = [((x >> 8).float() + 1.0) * (1.0 / 16777216.0) for x in r]  # (0, 1], fp32 exactly
+    two_pi = torch.tensor(6.2831853071795864769, dtype=torch.float32)
+    r0, r1 = torch.sqrt(-2.0 * torch.log(u[0])), torch.sqrt(-2.0 * torch.log(u[2]))
+    a0, a1 = two_pi * u[1], two_pi * u[3]
+    z = torch.stack([r0 * torch.cos(a0), r0 * torch.sin(a0), r1 * torch.cos(a1), r1 * torch.sin(a1)], 1)
+    lo = offset - 4 * q0
+    return z.reshape(-1)[lo:lo + n]
+
+
+def apply_update(out, center, delta, std=0.0, seed=0, round=0, offset=0):
+    o = delta if center is None else center + delta
+    if std != 0.0:
+        o = o + torch.tensor(std, dtype=torch.float32) * update_noise(out.numel(), seed, round, offset)
+    out.copy_(o)
+
+
 def mse_kl(xr, x, mu, lv, kl_w=1.0):
     mse = ((xr - x) ** 2).sum()
     kl = -0.5 * (1 + lv - mu * mu - lv.exp()).sum()
