@@ -30,6 +30,12 @@ class FLConfig:
     noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
     agg_weighting: str = "samples"  # clipped: samples (n_k / n) | uniform (1 / K)
     dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
+    prox_mu: float = 0.0           # FedProx: mu of the proximal term mu/2 |w - w_global|^2 (0 = off)
+    server_opt: str | None = None  # FedOpt server optimizer: fedavgm | fedadagrad | fedadam | fedyogi
+    server_lr: float | None = None  # its step size (default 1.0 for fedavgm, 0.01 for the adaptive ones)
+    server_beta1: float = 0.9
+    server_beta2: float = 0.99
+    server_tau: float = 1e-3       # adaptivity floor of fedadagrad / fedadam / fedyogi
     attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider
     malicious: int = 0             # number of malicious clients (ids 0..malicious-1)
     dropout: float = 0.0
@@ -61,7 +67,12 @@ def build_server(cfg: FLConfig, ctx):
                           "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
                           "weighting": cfg.agg_weighting}, attack=attack, ctx=ctx,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
-              straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline)
+              straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline, prox_mu=cfg.prox_mu)
+    if cfg.server_opt:
+        so = {"beta1": cfg.server_beta1, "beta2": cfg.server_beta2, "tau": cfg.server_tau}
+        if cfg.server_lr is not None:
+            so["lr"] = cfg.server_lr
+        kw.update(server_opt=cfg.server_opt, server_opt_kwargs=so)
     if algo is FedAvg:
         kw.update(batch_size=cfg.batch_size, local_epochs=cfg.local_epochs)
     return algo(model_fn, DeviceImageDataset(train, ctx.device), parts, **kw)

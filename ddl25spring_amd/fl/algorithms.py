@@ -24,6 +24,7 @@ from ..utils.metrics import PhaseTimer
 from .aggregate import MeanAggregator, make_aggregator
 from .local import LocalTrainer
 from .result import RunResult
+from .server_opt import make_server_opt
 
 
 def _sync(dev):
@@ -40,7 +41,16 @@ class FederatedBase:
                  weight_decay: float = 0.0, planner: str = "native", use_graph=None,
                  init_fn=None, eval_every: int = 1, eval_limit: int | None = None, name=None,
                  agg_kwargs=None, dropout: float = 0.0, stragglers: float = 0.0,
-                 straggler_slowdown: float = 4.0, deadline: float | None = None):
+                 straggler_slowdown: float = 4.0, deadline: float | None = None, prox_mu: float = 0.0,
+                 server_opt=None, server_opt_kwargs=None):
+        # [NS] heterogeneity: FedProx's proximal term mu/2 |w - w_global|^2 in every client's
+        # objective (Li et al. 2020), and a FedOpt server optimizer stepping w_global with the
+        # aggregate update as pseudo-gradient (Reddi et al. 2021); both off by default
+        if prox_mu < 0.0:
+            raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
+        self.prox_mu = float(prox_mu)
+        self.server_opt = make_server_opt(server_opt, **(server_opt_kwargs or {})) \
+            if isinstance(server_opt, str) else server_opt
         self.ctx = ctx or rdist.context()
         self.dev = self.ctx.device
         self.data = train_data
@@ -132,6 +142,8 @@ class FederatedBase:
             sd["attack"] = self.attack.state_dict()
         if hasattr(self.aggregator, "state_dict"):  # e.g. ClippedMean's noise round counter
             sd["aggregator"] = self.aggregator.state_dict()
+        if self.server_opt is not None:  # the moments m, v: flat rows in this run's parameter layout
+            sd["server_opt"] = self.server_opt.state_dict()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -159,6 +171,8 @@ class FederatedBase:
             self.attack.load_state_dict(sd["attack"])
         if "aggregator" in sd and hasattr(self.aggregator, "load_state_dict"):
             self.aggregator.load_state_dict(sd["aggregator"])
+        if self.server_opt is not None and "server_opt" in sd:
+            self.server_opt.load_state_dict(sd["server_opt"], like=self.w_global, fix=fix)
 
     # ------------------------------------------------------------------ helpers
     def _assign(self, chosen):
@@ -235,7 +249,9 @@ class FedAvg(FederatedBase):
             lt = self.attack.label_transform_for(mine, self.net.num_classes)
         if self.trainer is None:
             self.trainer = LocalTrainer(self.net, self.data, self.lr, self.B, self.momentum,
-                                        self.weight_decay, self.planner, self.use_graph)
+                                        self.weight_decay, self.planner, self.use_graph,
+                                        prox_mu=self.prox_mu,
+                                        anchor=self.w_global if self.prox_mu > 0.0 else None)
             self._graph_default = self.trainer.use_graph
         self.trainer.label_transform = lt
         # a label transform is graph-captured only if it declares a graph_key (pure device ops,
@@ -299,6 +315,8 @@ class FedAvg(FederatedBase):
         return dt, samples
 
     def _aggregate(self, rows, coeffs, counts):
+        if self.server_opt is not None:
+            return self._aggregate_server_opt(rows, coeffs, counts)
         if getattr(self.aggregator, "takes_center", False):
             # clipped mean: updates against w_global, clipped, averaged and added back in place
             self.aggregator(self.ctx, rows, coeffs, self.w_global, center=self.w_global, counts=counts)
@@ -309,6 +327,34 @@ class FedAvg(FederatedBase):
             agg = self.aggregator(self.ctx, upd, counts, self.w_global.numel(), keys=self._row_keys(counts))
             self.w_global.add_(agg)
 
+    # one launch for sum + server step where the plain mean needs no cross-rank route (off: the
+    # scratch-row route, which the tests hold bit-equal to it)
+    fuse_server_opt = True
+
+    def _aggregate_server_opt(self, rows, coeffs, counts):
+        """The aggregator's result goes to a scratch row instead of w_global; the server optimizer
+        then steps w_global towards it. m, v are replicated: every rank holds the same aggregate
+        after the aggregator's own cross-rank route and steps identically."""
+        opt, agg = self.server_opt, self.aggregator
+        plain = type(agg) is MeanAggregator
+        if plain and self.fuse_server_opt and not self.ctx.is_distributed and rows.shape[0] \
+                and rows.stride(1) == 1:
+            opt.step_rows(rows, coeffs, self.w_global)
+            return
+        target = getattr(self, "_opt_target", None)
+        if target is None:
+            target = self._opt_target = torch.empty_like(self.w_global)
+        if getattr(agg, "takes_center", False):  # clipped mean: target = w_global + clipped update
+            agg(self.ctx, rows, coeffs, target, center=self.w_global, counts=counts)
+            opt.step(self.w_global, target, False)
+        elif not getattr(agg, "needs_all", False):
+            agg(self.ctx, rows, coeffs, target)
+            opt.step(self.w_global, target, False)
+        else:  # robust rules act on updates: their result already is the delta
+            upd = rows - self.w_global
+            target.copy_(agg(self.ctx, upd, counts, self.w_global.numel(), keys=self._row_keys(counts)))
+            opt.step(self.w_global, target, True)
+
 
 class FedSGD(FederatedBase):
     """Clients return the full-local-batch gradient at w_global; the server takes one SGD step
@@ -318,6 +364,10 @@ class FedSGD(FederatedBase):
     def __init__(self, *a, max_microbatch: int = 4096, **kw):
         kw.setdefault("batch_size", -1)
         super().__init__(*a, **kw)
+        if self.prox_mu > 0.0:
+            raise ValueError("FedSGD: the proximal term vanishes at w_global, prox_mu has no effect")
+        if self.server_opt is not None:
+            raise ValueError("FedSGD: a server optimizer on gradients is not supported (use FedAvg)")
         self.max_mb = max_microbatch
         self.g_global = torch.zeros_like(self.w_global)
 

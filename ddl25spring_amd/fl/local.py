@@ -45,14 +45,22 @@ KEEP_GRAPH = os.environ.get("DDL_GRAPH_KEEP", "0") == "1"
 class LocalTrainer:
     def __init__(self, net, data, lr: float, batch_size: int, momentum: float = 0.0,
                  weight_decay: float = 0.0, planner: str = "native", use_graph: bool | None = None,
-                 label_transform=None, direct: bool | None = None):
+                 label_transform=None, direct: bool | None = None, prox_mu: float = 0.0, anchor=None):
         self.net, self.data = net, data
         self.B = batch_size
-        self.opt = optim.SGD(net, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.opt = optim.SGD(net, lr=lr, momentum=momentum, weight_decay=weight_decay, prox_mu=prox_mu)
+        if prox_mu > 0.0:
+            # FedProx: the anchor is the server's w_global tensor itself, updated in place between
+            # rounds, so a captured round graph keeps reading the current server model
+            if anchor is None:
+                raise ValueError("LocalTrainer(prox_mu > 0) needs the anchor tensor (the server model)")
+            self.opt.set_anchor(anchor)
         self.planner = planner
         dev = net.device
         self.use_graph = (dev.type == "cuda") if use_graph is None else (use_graph and dev.type == "cuda")
-        eligible = momentum == 0.0 and weight_decay == 0.0 and net.store.n_direct > 0 \
+        # the direct path cannot add the proximal term exactly (the WGRAD has already stepped the
+        # weights when the optimizer launch runs): FedProx takes the gradient-buffer path
+        eligible = momentum == 0.0 and weight_decay == 0.0 and prox_mu == 0.0 and net.store.n_direct > 0 \
             and getattr(net, "grad_hook", None) is None
         self.direct = eligible and (DIRECT_SGD and dev.type == "cuda" if direct is None else direct)
         self.label_transform = label_transform  # callable(y [G,B], g0, g1) -> y (attacks); with a

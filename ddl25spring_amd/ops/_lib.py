@@ -109,6 +109,12 @@ class SGDDirectArgs(ctypes.Structure):
                 ("lr", f32), ("grad_scale", f32)]
 
 
+class SGDProxArgs(ctypes.Structure):  # fedopt.hip
+    _fields_ = [("p", vp), ("g", vp), ("mom", vp), ("shadow", vp), ("anchor", vp), ("rows", i64),
+                ("P", i64), ("lr", f32), ("wd", f32), ("momentum", f32), ("dampening", f32),
+                ("grad_scale", f32), ("mu", f32), ("nesterov", i32), ("first_step", i32)]
+
+
 class AdamArgs(ctypes.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("shadow", vp), ("n", i64),
                 ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("wd", f32),
@@ -176,6 +182,10 @@ _SIGS = {
     "ddl_clip_scales": [vp, vp, i32, f64, vp, vp, vp],
     "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
     "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
+    # fedopt.hip
+    "ddl_sgd_prox": [ctypes.POINTER(SGDProxArgs), vp],
+    "ddl_server_opt": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
+    "ddl_server_opt_rows": [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
 }
 
 # fp32-activation twins of the templated memory-bound launchers (nn_ops.hip): same signatures
@@ -262,6 +272,7 @@ def kernels():
                                    ("SGDArgs", "ddl_sgd_args_size", SGDArgs),
                                    ("SGDDirectArgs", "ddl_sgd_direct_args_size", SGDDirectArgs),
                                    ("AdamArgs", "ddl_adam_args_size", AdamArgs),
+                                   ("SGDProxArgs", "ddl_sgd_prox_args_size", SGDProxArgs),
                                    ("ConvF32Args", "ddl_convf32_args_size", ConvF32Args),
                                    ("BNFArgs", "ddl_bnf_args_size", BNFArgs),
                                    ("BNFBwdArgs", "ddl_bnf_bwd_args_size", BNFBwdArgs),

@@ -1221,6 +1221,90 @@ def sgd_direct_step(p, g, shadow, dmap, lr: float, grad_scale: float = 1.0):
     check(_lib.kernels().ddl_sgd_direct(ctypes.byref(a), stream()), "sgd_direct")
 
 
+def sgd_prox_step(p, g, mom, shadow, anchor, lr, mu, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False,
+                  first_step=False, grad_scale=1.0):
+    """The FedProx local step (Li et al. 2020) over contiguous rows p/g/mom/shadow [G, P] with one
+    anchor [P] (the round's w_global): ``d = g * grad_scale + wd * p + mu * (p - anchor)``, momentum
+    / dampening / nesterov as ``sgd_step``, ``p -= lr * d``, shadow refreshed. One launch."""
+    assert p.dim() == 2 and p.shape == g.shape and anchor.numel() == p.shape[1]
+    if not p.is_cuda:
+        ref.sgd_prox(p, g, mom, shadow, anchor.reshape(1, -1), lr, wd, momentum, dampening, nesterov,
+                     first_step, grad_scale, mu)
+        return
+    assert p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and anchor.is_contiguous()
+    assert mom is None or (mom.is_contiguous() and mom.shape == p.shape)
+    assert shadow is None or (shadow.is_contiguous() and shadow.shape == p.shape)
+    if momentum != 0.0 and mom is None:
+        raise ValueError("sgd_prox_step: momentum needs a momentum buffer")
+    if p.numel() == 0:
+        return
+    a = _lib.SGDProxArgs()
+    a.p, a.g, a.mom, a.shadow, a.anchor = ptr(p), ptr(g), ptr(mom), ptr(shadow), ptr(anchor)
+    a.rows, a.P = p.shape
+    a.lr, a.wd, a.momentum, a.dampening, a.grad_scale, a.mu = lr, wd, momentum, dampening, grad_scale, mu
+    a.nesterov, a.first_step = int(nesterov), int(first_step)
+    check(_lib.kernels().ddl_sgd_prox(ctypes.byref(a), stream()), "sgd_prox")
+
+
+SERVER_OPT_KINDS = ref.SERVER_OPT_KINDS  # sgdm (FedAvgM), adagrad, adam, yogi
+
+
+def _server_opt_check(w, m, v, kind, lr, tau):
+    if kind not in SERVER_OPT_KINDS:
+        raise ValueError(f"server optimizer kind must be one of {sorted(SERVER_OPT_KINDS)}, got {kind!r}")
+    if not lr > 0.0:
+        raise ValueError(f"server_opt: lr must be positive, got {lr}")
+    if kind != "sgdm" and not tau > 0.0:
+        raise ValueError(f"server_opt: tau must be positive, got {tau}")
+    n = w.numel()
+    for t in (w, m) + (() if kind == "sgdm" else (v,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    return n
+
+
+def server_opt_step(w, x, m, v, kind: str, x_is_delta: bool, lr: float, beta1: float = 0.9,
+                    beta2: float = 0.99, tau: float = 1e-3):
+    """One FedOpt server step (Reddi et al. 2021, Algorithm 2, no bias correction) in place on
+    w, m, v [n]: ``delta = x if x_is_delta else x - w``; ``sgdm``: m = b1 m + delta, w += lr m (v is
+    not touched and may be None); ``adagrad`` / ``adam`` / ``yogi``: m = b1 m + (1 - b1) delta, v by
+    the kind's rule, w += lr m / (sqrt(v) + tau). All fp32, every operation rounded on its own; a
+    coordinate whose delta is NaN / Inf keeps its w, m, v."""
+    lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
+    n = _server_opt_check(w, m, v, kind, lr, tau)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n
+    if n == 0:
+        return w
+    if not w.is_cuda:
+        ref.server_opt(w, x, m, v, kind, x_is_delta, lr, beta1, beta2, tau)
+        return w
+    check(_lib.kernels().ddl_server_opt(ptr(w), ptr(x), ptr(m), ptr(v), n, SERVER_OPT_KINDS[kind],
+                                        int(bool(x_is_delta)), lr, beta1, beta2, tau, stream()), "server_opt")
+    return w
+
+
+def server_opt_rows(rows, coeff, w, m, v, kind: str, lr: float, beta1: float = 0.9, beta2: float = 0.99,
+                    tau: float = 1e-3, x_is_delta: bool = False):
+    """``server_opt_step`` on ``x = sum_g coeff[g] * rows[g]`` formed in registers (rows [G, n] may be
+    strided views with unit inner stride): the bits of ``weighted_sum`` into a temporary followed by
+    ``server_opt_step``, in one launch that moves (G + 6) n floats instead of (G + 8) n."""
+    lr, beta1, beta2, tau = float(lr), float(beta1), float(beta2), float(tau)
+    n = _server_opt_check(w, m, v, kind, lr, tau)
+    G = rows.shape[0]
+    assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == n and G >= 1
+    assert coeff.numel() == G
+    if n == 0:
+        return w
+    if not w.is_cuda:
+        ref.server_opt_rows(rows, coeff, w, m, v, kind, x_is_delta, lr, beta1, beta2, tau)
+        return w
+    assert rows.stride(1) == 1
+    coeff = coeff.float().contiguous()
+    check(_lib.kernels().ddl_server_opt_rows(ptr(rows), rows.stride(0), ptr(coeff), G, ptr(w), ptr(m), ptr(v),
+                                             n, SERVER_OPT_KINDS[kind], int(bool(x_is_delta)), lr, beta1,
+                                             beta2, tau, stream()), "server_opt_rows")
+    return w
+
+
 def adam_step(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, decoupled, grad_scale=1.0,
               step_dev=None, row_len: int = 0):
     """One fused Adam/AdamW pass over flat buffers. ``step_dev`` (int64 [1] on the device, already

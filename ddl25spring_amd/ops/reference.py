@@ -405,6 +405,64 @@ def clipped_sum(rows, center, cs, out, accumulate=False):
     out.copy_(acc)
 
 
+# ------------------------------------------------ FedProx / FedOpt (fedopt.hip), fp32 torch twins
+def _s32(x):
+    return torch.tensor(float(x), dtype=torch.float32)
+
+
+def sgd_prox(p, g, mom, shadow, anchor, lr, wd, momentum, dampening, nesterov, first_step, grad_scale=1.0,
+             mu=0.0):
+    """Rows p/g/mom/shadow [G, P], anchor [P]: every operation a separate fp32 rounding, in
+    sgd_prox_kernel's order."""
+    lr, wd, mo, gs, mu = (_s32(v) for v in (lr, wd, momentum, grad_scale, mu))
+    d = g * gs + wd * p
+    d = d + mu * (p - anchor)
+    if momentum != 0:
+        if first_step:
+            mom.copy_(d)
+        else:
+            mom.copy_(mo * mom + (_s32(1.0) - _s32(dampening)) * d)
+        d = d + mo * mom if nesterov else mom
+    p.copy_(p - lr * d)
+    if shadow is not None:
+        shadow.copy_(p.to(shadow.dtype))
+
+
+SERVER_OPT_KINDS = {"sgdm": 0, "adagrad": 1, "adam": 2, "yogi": 3}
+
+
+def server_opt(w, x, m, v, kind, x_is_delta, lr, beta1, beta2, tau):
+    """In place on w, m, v [n] (fedopt.hip server_opt_kernel, the same operation order); a
+    coordinate whose delta is NaN / Inf keeps its w, m, v."""
+    lr, b1, b2, tau = (_s32(s) for s in (lr, beta1, beta2, tau))
+    d = x if x_is_delta else x - w
+    ok = torch.isfinite(d)
+    d = torch.where(ok, d, torch.zeros_like(d))
+    if kind == "sgdm":
+        m1 = b1 * m + d
+        w1 = w + lr * m1
+    else:
+        omb1, omb2 = _s32(1.0) - b1, _s32(1.0) - b2
+        m1 = b1 * m + omb1 * d
+        if kind == "adagrad":
+            v1 = v + d * d
+        elif kind == "adam":
+            v1 = b2 * v + omb2 * d * d
+        else:
+            d2 = d * d
+            v1 = v - omb2 * d2 * torch.sign(v - d2)
+        w1 = w + lr * m1 / (v1.sqrt() + tau)
+        v.copy_(torch.where(ok, v1, v))
+    m.copy_(torch.where(ok, m1, m))
+    w.copy_(torch.where(ok, w1, w))
+
+
+def server_opt_rows(rows, coeff, w, m, v, kind, x_is_delta, lr, beta1, beta2, tau):
+    x = torch.empty_like(w)
+    weighted_sum(rows, coeff, x)
+    server_opt(w, x, m, v, kind, x_is_delta, lr, beta1, beta2, tau)
+
+
 CLIP_NOISE_TAG = 0x3C6EF372
 _M32 = 0xFFFFFFFF
 

@@ -50,15 +50,41 @@ class _Base:
 
 class SGD(_Base):
     def __init__(self, params, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False):
+                 weight_decay: float = 0.0, nesterov: bool = False, prox_mu: float = 0.0):
         super().__init__(params)
         self.lr, self.momentum, self.dampening = lr, momentum, dampening
         self.weight_decay, self.nesterov = weight_decay, nesterov
         self.mom = torch.zeros_like(self.store.data) if momentum else None
         self.steps = 0
+        # FedProx (Li et al. 2020): the gradient gains prox_mu * (p - anchor), anchor [P] shared by
+        # every client slot (the round's server model)
+        if prox_mu < 0.0:
+            raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
+        self.prox_mu = float(prox_mu)
+        self.anchor = None
+
+    def set_anchor(self, anchor: torch.Tensor):
+        """The proximal term's anchor [P]; the tensor itself is kept (not copied), so updating it
+        in place between rounds moves the anchor, also inside a captured graph."""
+        if anchor.shape != self.store.data.shape[1:] or anchor.dtype != torch.float32 \
+                or not anchor.is_contiguous():
+            raise ValueError("set_anchor: a contiguous fp32 tensor of one parameter row is needed")
+        self.anchor = anchor
+        return self
 
     def step(self, grad_scale: float = 1.0):
         st = self.store
+        if self.prox_mu > 0.0:
+            if self.anchor is None:
+                raise RuntimeError("SGD(prox_mu > 0): call set_anchor() before step()")
+            Fn.sgd_prox_step(self._rows(st.data), self._rows(st.grad),
+                             None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
+                             self.anchor, self.lr, self.prox_mu, self.weight_decay, self.momentum,
+                             self.dampening, self.nesterov, first_step=(self.steps == 0),
+                             grad_scale=grad_scale)
+            st._shadow_version = st.data._version
+            self.steps += 1
+            return
         Fn.sgd_step(self._rows(st.data), self._rows(st.grad),
                     None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
                     self.lr, self.weight_decay, self.momentum, self.dampening, self.nesterov,
@@ -71,7 +97,7 @@ class SGD(_Base):
         (``ParamStore.direct_update``): shadow refresh for those, plain SGD + gradient zeroing for
         the rest, in one launch. Only for momentum- and weight-decay-free SGD, unscaled gradients
         (the WGRAD launches already added the unscaled ``-lr * dW``)."""
-        assert self.mom is None and self.weight_decay == 0.0
+        assert self.mom is None and self.weight_decay == 0.0 and self.prox_mu == 0.0
         if grad_scale != 1.0:
             raise ValueError("step_direct: the direct columns were stepped unscaled inside the backward")
         st = self.store
