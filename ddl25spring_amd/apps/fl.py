@@ -12,7 +12,7 @@ import numpy as np
 
 @dataclass
 class FLConfig:
-    algorithm: str = "fedavg"      # fedavg | fedsgd | fedsgd_weight
+    algorithm: str = "fedavg"      # fedavg | fedsgd | fedsgd_weight | scaffold
     model: str = "mnist_cnn"       # mnist_cnn | mnist_mlp | resnet18 | resnet50
     dataset: str = "mnist"         # mnist | cifar10 | imagenet (real copy via DDL_DATA_ROOT, else synthetic)
     clients: int = 100
@@ -51,7 +51,7 @@ class FLConfig:
 def build_server(cfg: FLConfig, ctx):
     from ..data.images import DeviceImageDataset, load_images
     from ..data.split import split
-    from ..fl.algorithms import FedAvg, FedSGD, FedSgdWeight
+    from ..fl.algorithms import FedAvg, FedSGD, FedSgdWeight, Scaffold
     from ..fl.attacks import make_attack
     from ..models import mnist_cnn, mnist_mlp, resnet18_cifar, resnet50_imagenet
     train = load_images(cfg.dataset, True, cfg.train_size, seed=cfg.seed)
@@ -60,7 +60,8 @@ def build_server(cfg: FLConfig, ctx):
     model_fn = {"mnist_cnn": mnist_cnn, "mnist_mlp": mnist_mlp, "resnet18": resnet18_cifar,
                 "resnet50": resnet50_imagenet}[cfg.model]
     attack = make_attack(cfg.attack, list(range(cfg.malicious))) if cfg.attack else None
-    algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight}[cfg.algorithm]
+    algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight,
+            "scaffold": Scaffold}[cfg.algorithm]
     kw = dict(lr=cfg.lr, client_fraction=cfg.client_fraction, seed=cfg.seed,
               test_data=DeviceImageDataset(test, ctx.device), aggregator=cfg.aggregator,
               agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": cfg.clip_norm,
@@ -73,7 +74,7 @@ def build_server(cfg: FLConfig, ctx):
         if cfg.server_lr is not None:
             so["lr"] = cfg.server_lr
         kw.update(server_opt=cfg.server_opt, server_opt_kwargs=so)
-    if algo is FedAvg:
+    if algo in (FedAvg, Scaffold):
         kw.update(batch_size=cfg.batch_size, local_epochs=cfg.local_epochs)
     return algo(model_fn, DeviceImageDataset(train, ctx.device), parts, **kw)
 

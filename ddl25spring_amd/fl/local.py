@@ -45,7 +45,8 @@ KEEP_GRAPH = os.environ.get("DDL_GRAPH_KEEP", "0") == "1"
 class LocalTrainer:
     def __init__(self, net, data, lr: float, batch_size: int, momentum: float = 0.0,
                  weight_decay: float = 0.0, planner: str = "native", use_graph: bool | None = None,
-                 label_transform=None, direct: bool | None = None, prox_mu: float = 0.0, anchor=None):
+                 label_transform=None, direct: bool | None = None, prox_mu: float = 0.0, anchor=None,
+                 control=None):
         self.net, self.data = net, data
         self.B = batch_size
         self.opt = optim.SGD(net, lr=lr, momentum=momentum, weight_decay=weight_decay, prox_mu=prox_mu)
@@ -55,13 +56,20 @@ class LocalTrainer:
             if anchor is None:
                 raise ValueError("LocalTrainer(prox_mu > 0) needs the anchor tensor (the server model)")
             self.opt.set_anchor(anchor)
+        if control is not None:
+            # SCAFFOLD: (c, bank, slot_client), the server's tensors themselves, updated in place
+            # between rounds, so a captured round graph keeps reading the current control variates
+            if prox_mu > 0.0:
+                raise ValueError("LocalTrainer: control variates (SCAFFOLD) and prox_mu > 0 are not combined")
+            self.opt.set_control(*control)
         self.planner = planner
         dev = net.device
         self.use_graph = (dev.type == "cuda") if use_graph is None else (use_graph and dev.type == "cuda")
         # the direct path cannot add the proximal term exactly (the WGRAD has already stepped the
-        # weights when the optimizer launch runs): FedProx takes the gradient-buffer path
-        eligible = momentum == 0.0 and weight_decay == 0.0 and prox_mu == 0.0 and net.store.n_direct > 0 \
-            and getattr(net, "grad_hook", None) is None
+        # weights when the optimizer launch runs): FedProx takes the gradient-buffer path, and so
+        # does SCAFFOLD's correction
+        eligible = momentum == 0.0 and weight_decay == 0.0 and prox_mu == 0.0 and control is None \
+            and net.store.n_direct > 0 and getattr(net, "grad_hook", None) is None
         self.direct = eligible and (DIRECT_SGD and dev.type == "cuda" if direct is None else direct)
         self.label_transform = label_transform  # callable(y [G,B], g0, g1) -> y (attacks); with a
         # ``graph_key`` attribute it is pure device ops and may be captured in the round graph

@@ -115,6 +115,13 @@ class SGDProxArgs(ctypes.Structure):  # fedopt.hip
                 ("grad_scale", f32), ("mu", f32), ("nesterov", i32), ("first_step", i32)]
 
 
+class SGDScaffoldArgs(ctypes.Structure):  # scaffold.hip
+    _fields_ = [("p", vp), ("g", vp), ("mom", vp), ("shadow", vp), ("c", vp), ("bank", vp),
+                ("slot_client", vp), ("rows", i64), ("P", i64), ("ld", i64), ("lr", f32), ("wd", f32),
+                ("momentum", f32), ("dampening", f32), ("grad_scale", f32), ("nesterov", i32),
+                ("first_step", i32)]
+
+
 class AdamArgs(ctypes.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("shadow", vp), ("n", i64),
                 ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("wd", f32),
@@ -186,6 +193,9 @@ _SIGS = {
     "ddl_sgd_prox": [ctypes.POINTER(SGDProxArgs), vp],
     "ddl_server_opt": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     "ddl_server_opt_rows": [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
+    # scaffold.hip
+    "ddl_sgd_scaffold": [ctypes.POINTER(SGDScaffoldArgs), vp],
+    "ddl_scaffold_finish": [vp, i64, vp, vp, vp, i64, vp, vp, i32, f32, vp, i64, i32, vp],
 }
 
 # fp32-activation twins of the templated memory-bound launchers (nn_ops.hip): same signatures
@@ -273,6 +283,7 @@ def kernels():
                                    ("SGDDirectArgs", "ddl_sgd_direct_args_size", SGDDirectArgs),
                                    ("AdamArgs", "ddl_adam_args_size", AdamArgs),
                                    ("SGDProxArgs", "ddl_sgd_prox_args_size", SGDProxArgs),
+                                   ("SGDScaffoldArgs", "ddl_sgd_scaffold_args_size", SGDScaffoldArgs),
                                    ("ConvF32Args", "ddl_convf32_args_size", ConvF32Args),
                                    ("BNFArgs", "ddl_bnf_args_size", BNFArgs),
                                    ("BNFBwdArgs", "ddl_bnf_bwd_args_size", BNFBwdArgs),

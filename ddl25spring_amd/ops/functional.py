@@ -1246,6 +1246,90 @@ def sgd_prox_step(p, g, mom, shadow, anchor, lr, mu, wd=0.0, momentum=0.0, dampe
     check(_lib.kernels().ddl_sgd_prox(ctypes.byref(a), stream()), "sgd_prox")
 
 
+def check_slot_clients(ids, n_clients: int):
+    """The host-side check of a SCAFFOLD slot table before it goes to the device: every id a bank
+    row (0 <= id < n_clients) and all distinct, so no two slots write one bank row. The kernels take
+    the table as it is. -> the ids as a list of ints."""
+    ids = [int(i) for i in ids]
+    if any(i < 0 or i >= n_clients for i in ids):
+        raise ValueError(f"slot_client: ids must lie in [0, {n_clients}), got {ids}")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"slot_client: two slots name one client, got {ids}")
+    return ids
+
+
+def _scaffold_bank_check(name, P, c, bank, slot_client, G):
+    assert c.dtype == torch.float32 and c.is_contiguous() and c.numel() == P
+    assert bank.dtype == torch.float32 and bank.dim() == 2 and bank.shape[1] == P
+    assert bank.shape[0] == 1 or bank.stride(0) >= P
+    assert slot_client.dtype == torch.int32 and slot_client.dim() == 1 and slot_client.numel() == G
+    assert slot_client.device == bank.device == c.device
+    if not slot_client.is_cuda:  # a host table is checked here; a device table where it was built
+        check_slot_clients(slot_client.tolist(), bank.shape[0])
+    if bank.is_cuda:
+        assert bank.stride(1) == 1 and slot_client.is_contiguous(), f"{name}: unit inner strides are needed"
+
+
+def sgd_scaffold_step(p, g, mom, shadow, c, bank, slot_client, lr, wd=0.0, momentum=0.0, dampening=0.0,
+                      nesterov=False, first_step=False, grad_scale=1.0):
+    """The SCAFFOLD local step (Karimireddy et al. 2020) over contiguous rows p/g/mom/shadow [G, P]:
+    ``d = g * grad_scale + wd * p + (c - bank[slot_client[row]])`` with the server control variate
+    c [P] and the clients' control variates bank [N, P] (rows may be strided), read in place through
+    the int32 table slot_client [G] on the rows' device; momentum / dampening / nesterov as
+    ``sgd_step``, ``p -= lr * d``, shadow refreshed. One launch."""
+    assert p.dim() == 2 and p.shape == g.shape
+    _scaffold_bank_check("sgd_scaffold_step", p.shape[1], c, bank, slot_client, p.shape[0])
+    if momentum != 0.0 and mom is None:
+        raise ValueError("sgd_scaffold_step: momentum needs a momentum buffer")
+    if not p.is_cuda:
+        ref.sgd_scaffold(p, g, mom, shadow, c, bank, slot_client, lr, wd, momentum, dampening, nesterov,
+                         first_step, grad_scale)
+        return
+    assert p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
+    assert mom is None or (mom.is_contiguous() and mom.shape == p.shape)
+    assert shadow is None or (shadow.is_contiguous() and shadow.shape == p.shape)
+    if p.numel() == 0:
+        return
+    a = _lib.SGDScaffoldArgs()
+    a.p, a.g, a.mom, a.shadow = ptr(p), ptr(g), ptr(mom), ptr(shadow)
+    a.c, a.bank, a.slot_client = ptr(c), ptr(bank), ptr(slot_client)
+    a.rows, a.P = p.shape
+    a.ld = bank.stride(0) if bank.shape[0] > 1 else p.shape[1]
+    a.lr, a.wd, a.momentum, a.dampening, a.grad_scale = lr, wd, momentum, dampening, grad_scale
+    a.nesterov, a.first_step = int(nesterov), int(first_step)
+    check(_lib.kernels().ddl_sgd_scaffold(ctypes.byref(a), stream()), "sgd_scaffold")
+
+
+def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c=False):
+    """SCAFFOLD's round-end update (option II) in one launch: for the trained rows y = rows [G, P]
+    (unit inner stride) of the clients slot_client [G], from the round's server model x [P],
+
+        delta_g = (x - y_g) * inv_klr[g] - c;   bank[slot_client[g]] += delta_g;
+        dc = sum_g delta_g * inv_n  (slots added from 0 upward, from 0),
+
+    and with ``apply_c`` also ``c += dc``. inv_klr [G] is fp32 on the rows' device (1 / (K_g lr) of
+    each slot). A coordinate whose delta is NaN / Inf leaves that bank entry untouched and adds
+    nothing. All fp32, every operation rounded on its own; (3G + 3) P floats moved."""
+    G, P = rows.shape
+    assert rows.dtype == torch.float32 and G >= 1
+    _scaffold_bank_check("scaffold_finish", P, c, bank, slot_client, G)
+    for t in (x, dc):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == P
+    assert inv_klr.dtype == torch.float32 and inv_klr.numel() == G and inv_klr.device == rows.device
+    if P == 0:
+        return dc
+    if not rows.is_cuda:
+        ref.scaffold_finish(rows, x, c, bank, slot_client, inv_klr, float(inv_n), dc, apply_c)
+        return dc
+    assert rows.stride(1) == 1 and inv_klr.is_contiguous()
+    ld = bank.stride(0) if bank.shape[0] > 1 else P
+    ldy = rows.stride(0) if G > 1 else P
+    check(_lib.kernels().ddl_scaffold_finish(ptr(rows), ldy, ptr(x), ptr(c), ptr(bank), ld, ptr(slot_client),
+                                             ptr(inv_klr), G, float(inv_n), ptr(dc), P, int(bool(apply_c)),
+                                             stream()), "scaffold_finish")
+    return dc
+
+
 SERVER_OPT_KINDS = ref.SERVER_OPT_KINDS  # sgdm (FedAvgM), adagrad, adam, yogi
 
 

@@ -463,6 +463,42 @@ def server_opt_rows(rows, coeff, w, m, v, kind, x_is_delta, lr, beta1, beta2, ta
     server_opt(w, x, m, v, kind, x_is_delta, lr, beta1, beta2, tau)
 
 
+# ------------------------------------------------------- SCAFFOLD (scaffold.hip), fp32 torch twins
+def sgd_scaffold(p, g, mom, shadow, c, bank, slot_client, lr, wd, momentum, dampening, nesterov, first_step,
+                 grad_scale=1.0):
+    """Rows p/g/mom/shadow [G, P], c [P], bank [N, P] (a view is fine), slot_client [G]: every
+    operation a separate fp32 rounding, in sgd_scaffold_kernel's order."""
+    lr, wd, mo, gs = (_s32(v) for v in (lr, wd, momentum, grad_scale))
+    d = g * gs + wd * p
+    d = d + (c.reshape(1, -1) - bank[slot_client.long()])
+    if momentum != 0:
+        if first_step:
+            mom.copy_(d)
+        else:
+            mom.copy_(mo * mom + (_s32(1.0) - _s32(dampening)) * d)
+        d = d + mo * mom if nesterov else mom
+    p.copy_(p - lr * d)
+    if shadow is not None:
+        shadow.copy_(p.to(shadow.dtype))
+
+
+def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c):
+    """scaffold_finish_kernel's order: the slots from 0 upward, acc from 0; a NaN / Inf delta
+    leaves its bank entry untouched and adds nothing."""
+    inv_n = _s32(inv_n)
+    acc = torch.zeros_like(x)
+    for g, cl in enumerate(slot_client.tolist()):
+        t = (x - rows[g]) * inv_klr[g]
+        delta = t - c
+        ok = torch.isfinite(delta)
+        delta = torch.where(ok, delta, torch.zeros_like(delta))
+        bank[cl].copy_(torch.where(ok, bank[cl] + delta, bank[cl]))
+        acc = torch.where(ok, acc + delta * inv_n, acc)
+    dc.copy_(acc)
+    if apply_c:
+        c.copy_(c + acc)
+
+
 CLIP_NOISE_TAG = 0x3C6EF372
 _M32 = 0xFFFFFFFF
 

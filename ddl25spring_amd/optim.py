@@ -62,6 +62,7 @@ class SGD(_Base):
             raise ValueError(f"prox_mu must be >= 0, got {prox_mu}")
         self.prox_mu = float(prox_mu)
         self.anchor = None
+        self.control = None  # SCAFFOLD: (c, bank, slot_client), see set_control
 
     def set_anchor(self, anchor: torch.Tensor):
         """The proximal term's anchor [P]; the tensor itself is kept (not copied), so updating it
@@ -72,8 +73,36 @@ class SGD(_Base):
         self.anchor = anchor
         return self
 
+    def set_control(self, c: torch.Tensor, bank: torch.Tensor, slot_client: torch.Tensor):
+        """SCAFFOLD (Karimireddy et al. 2020): the gradient gains c - bank[slot_client[slot]], with
+        the server control variate c [P], the clients' bank [N, P] and the int32 table slot_client
+        [G] (slot -> client id). The tensors themselves are kept (not copied), so updating them in
+        place between rounds moves the correction, also inside a captured graph."""
+        if self.prox_mu > 0.0:
+            raise ValueError("SGD: SCAFFOLD's control variates and prox_mu > 0 are not combined")
+        P = self.store.data.shape[1]
+        if c.shape != (P,) or c.dtype != torch.float32 or not c.is_contiguous():
+            raise ValueError("set_control: c must be a contiguous fp32 tensor of one parameter row")
+        if bank.dim() != 2 or bank.shape[1] != P or bank.dtype != torch.float32 or bank.stride(1) != 1:
+            raise ValueError("set_control: bank must be fp32 [clients, P] with unit inner stride")
+        if slot_client.shape != (self.store.G,) or slot_client.dtype != torch.int32 \
+                or not slot_client.is_contiguous():
+            raise ValueError("set_control: slot_client must be a contiguous int32 tensor of one entry per slot")
+        self.control = (c, bank, slot_client)
+        return self
+
     def step(self, grad_scale: float = 1.0):
         st = self.store
+        if self.control is not None:
+            c, bank, slot_client = self.control
+            Fn.sgd_scaffold_step(self._rows(st.data), self._rows(st.grad),
+                                 None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
+                                 c, bank, self._rows(slot_client), self.lr, self.weight_decay, self.momentum,
+                                 self.dampening, self.nesterov, first_step=(self.steps == 0),
+                                 grad_scale=grad_scale)
+            st._shadow_version = st.data._version
+            self.steps += 1
+            return
         if self.prox_mu > 0.0:
             if self.anchor is None:
                 raise RuntimeError("SGD(prox_mu > 0): call set_anchor() before step()")
@@ -97,7 +126,7 @@ class SGD(_Base):
         (``ParamStore.direct_update``): shadow refresh for those, plain SGD + gradient zeroing for
         the rest, in one launch. Only for momentum- and weight-decay-free SGD, unscaled gradients
         (the WGRAD launches already added the unscaled ``-lr * dW``)."""
-        assert self.mom is None and self.weight_decay == 0.0 and self.prox_mu == 0.0
+        assert self.mom is None and self.weight_decay == 0.0 and self.prox_mu == 0.0 and self.control is None
         if grad_scale != 1.0:
             raise ValueError("step_direct: the direct columns were stepped unscaled inside the backward")
         st = self.store
