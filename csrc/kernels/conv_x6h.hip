@@ -38,6 +38,13 @@ constexpr int PSTR = 112;   // weight image bytes per row
 constexpr int PQ = 7;       // quads per pixel / row
 constexpr int HBSMALL = 32768;  // halo image bytes, OW >= 8 (2 workgroups per CU at BP 128: 48 + 32 KiB)
 constexpr int HBLARGE = 45056;  // OW = 4 (8 image segments of 6 x 6 pixels)
+// BP 64 only: with its 24 KiB weight ring, 3 x (24,576 + 26,624) = 153,600 B <= 160 KiB, so three
+// workgroups share a CU (three waves per SIMD, __launch_bounds__(256, 3)). The 32- and 16-wide
+// layouts (and the 8-wide ones halo_layout finds within it) fit; the others keep HBSMALL at two.
+constexpr int HBTINY = 26624;
+// instances that run three per CU: the 3x3 DGRAD (181 VGPRs unconstrained) would spill under the
+// 168-register cap, so it stays on HBSMALL
+constexpr bool x6h_has_tiny(int mode, int bp, int rs) { return bp == 64 && !(mode == F_DGRAD && rs == 3); }
 constexpr int NWB = 3;      // weight images in the LDS ring (DMA runs two steps ahead)
 // Precision note: the bf16 MFMA's internal accumulation is biased (not round-to-nearest). Long
 // chains into one accumulator (one per 16-channel chunk = 54 MFMAs) left a ~3e-6 relative
@@ -293,12 +300,12 @@ __device__ __forceinline__ void fepi_t(const ConvF32Args& a, const FGeo& o, f16v
 }
 
 template <int MODE, int BP, int RS, int HB, bool PADW>
-__global__ __launch_bounds__(256, 2) void convx6h_kernel(ConvF32Args a, HaloGeo hg) {
+__global__ __launch_bounds__(256, HB == HBTINY ? 3 : 2) void convx6h_kernel(ConvF32Args a, HaloGeo hg) {
   constexpr int T = RS * RS;                 // taps
   constexpr int PD = (RS - 1) / 2;           // pad
   constexpr int WP = BP / 2, TI = WP / 32, TJ = 2;
   constexpr int UP = BP / 32;                // weight LDS-DMA pieces (1 KiB) per wave per step
-  constexpr int HPM = HB == HBSMALL ? 208 : 288;   // halo pixel capacity (host-checked)
+  constexpr int HPM = HB == HBLARGE ? 288 : 208;   // halo pixel capacity (host-checked)
   constexpr int NUH = (HPM * 4 + 255) / 256;  // halo units (pixel x 4-channel chunk) per thread
   constexpr int PIMG = BP * 128;             // bytes per weight image slot (BP * 112 used)
   constexpr bool XF_OK = MODE == F_FWD;
@@ -860,8 +867,7 @@ static bool x6h_geo(const ConvF32Args& a, int mode, int bp, HaloGeo& h, int& rs)
     return e ? atoi(e) : 0;
   }();
   h.probe = probe;
-  // the instance is chosen by x6h_large(): a halo of more than 208 pixels (e.g. 64-wide images: two
-  // rows of 66) runs on the large instance even when its bytes would fit the small one
+  // the instance is chosen by x6h_tier()
   if (h.HBYTES > HBLARGE || h.HP > 288) return false;
   return true;
 }
@@ -886,20 +892,72 @@ static int launch_x6h(ConvF32Args a, const HaloGeo& h, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-template <int MODE, int HB, bool PADW>
-static int dispatch_rs(const ConvF32Args& a, int bp, int rs, const HaloGeo& h, hipStream_t s) {
-  if (rs == 3)
-    return bp == 128 ? launch_x6h<MODE, 128, 3, HB, PADW>(a, h, s) : launch_x6h<MODE, 64, 3, HB, PADW>(a, h, s);
-  return bp == 128 ? launch_x6h<MODE, 128, 1, HB, PADW>(a, h, s) : launch_x6h<MODE, 64, 1, HB, PADW>(a, h, s);
+// LDS size class of a launch: HBLARGE for a halo of more than 208 pixels (e.g. 64-wide images: two
+// rows of 66) even when its bytes would fit a smaller one; HBTINY (three workgroups per CU) when
+// the layout halo_layout chose fits it and the instance exists; else HBSMALL
+static int x6h_tier(const HaloGeo& h, int mode, int bp, int rs) {
+  if (h.HBYTES > HBSMALL || h.HP > 208) return HBLARGE;
+  return x6h_has_tiny(mode, bp, rs) && h.HBYTES <= HBTINY ? HBTINY : HBSMALL;
 }
-template <int MODE, int HB>
-static int dispatch_hb(const ConvF32Args& a, int bp, int rs, const HaloGeo& h, hipStream_t s) {
-  return h.OWr != (1 << h.lgW) ? dispatch_rs<MODE, HB, true>(a, bp, rs, h, s) : dispatch_rs<MODE, HB, false>(a, bp, rs, h, s);
+
+// f(instance) for the instance (MODE, bp, rs, hb, padw), -1 where there is none
+template <template <int, int, int, int, bool> class F, int MODE, int BP, int RS, int HB, typename... A>
+static int x6h_pick_padw(bool padw, A&&... args) {
+  if constexpr (HB == HBTINY && !x6h_has_tiny(MODE, BP, RS)) return -1;
+  else return padw ? F<MODE, BP, RS, HB, true>::run(args...) : F<MODE, BP, RS, HB, false>::run(args...);
 }
-static bool x6h_large(const HaloGeo& h) { return h.HBYTES > HBSMALL || h.HP > 208; }
+template <template <int, int, int, int, bool> class F, int MODE, int HB, typename... A>
+static int x6h_pick_bp(int bp, int rs, bool padw, A&&... args) {
+  if (rs != 1 && rs != 3) return -1;
+  if (bp == 128)
+    return rs == 3 ? x6h_pick_padw<F, MODE, 128, 3, HB>(padw, args...) : x6h_pick_padw<F, MODE, 128, 1, HB>(padw, args...);
+  if (bp == 64)
+    return rs == 3 ? x6h_pick_padw<F, MODE, 64, 3, HB>(padw, args...) : x6h_pick_padw<F, MODE, 64, 1, HB>(padw, args...);
+  return -1;
+}
+template <template <int, int, int, int, bool> class F, int MODE, typename... A>
+static int x6h_pick(int bp, int rs, int hb, bool padw, A&&... args) {
+  if (hb == HBLARGE) return x6h_pick_bp<F, MODE, HBLARGE>(bp, rs, padw, args...);
+  if (hb == HBSMALL) return x6h_pick_bp<F, MODE, HBSMALL>(bp, rs, padw, args...);
+  if (hb == HBTINY) return x6h_pick_bp<F, MODE, HBTINY>(bp, rs, padw, args...);
+  return -1;
+}
+
+template <int MODE, int BP, int RS, int HB, bool PADW>
+struct X6hLaunch {
+  static int run(const ConvF32Args& a, const HaloGeo& h, hipStream_t s) { return launch_x6h<MODE, BP, RS, HB, PADW>(a, h, s); }
+};
+template <int MODE, int BP, int RS, int HB, bool PADW>
+struct X6hResidency {
+  static int run() {
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, convx6h_kernel<MODE, BP, RS, HB, PADW>, 256, 0) == hipSuccess ? n : -1;
+  }
+};
+
 template <int MODE>
 static int dispatch_x6h(const ConvF32Args& a, int bp, int rs, const HaloGeo& h, hipStream_t s) {
-  return x6h_large(h) ? dispatch_hb<MODE, HBLARGE>(a, bp, rs, h, s) : dispatch_hb<MODE, HBSMALL>(a, bp, rs, h, s);
+  const int r = x6h_pick<X6hLaunch, MODE>(bp, rs, x6h_tier(h, MODE, bp, rs), h.OWr != (1 << h.lgW), a, h, s);
+  return r < 0 ? (int)hipErrorInvalidValue : r;
+}
+
+// Workgroups of 256 threads one CU holds of the instance (hipOccupancyMaxActiveBlocksPerMultiprocessor);
+// tier = its LDS size class in bytes (26624 / 32768 / 45056); -1: no such instance
+DDL_API int ddl_x6h_residency(int mode, int bp, int rs, int tier, int padw) {
+  if (mode == F_FWD) return x6h_pick<X6hResidency, F_FWD>(bp, rs, tier, padw != 0);
+  if (mode == F_DGRAD) return x6h_pick<X6hResidency, F_DGRAD>(bp, rs, tier, padw != 0);
+  return -1;
+}
+
+// The halo layout of a launch (host only): out[0..4] = ROWB, SEGB, HBYTES, HP, LDS size class in
+// bytes; 0, or -1 when the kernel declines the geometry
+DDL_API int ddl_x6h_layout(const ConvF32Args* ap, int mode, int cfg, int* out) {
+  HaloGeo h;
+  int rs;
+  const int bp = (cfg & 0xff) * 16;
+  if (!x6h_geo(*ap, mode, bp, h, rs)) return -1;
+  out[0] = h.ROWB; out[1] = h.SEGB; out[2] = h.HBYTES; out[3] = h.HP; out[4] = x6h_tier(h, mode, bp, rs);
+  return 0;
 }
 
 // Statistics / BN-reduce slots of a halo launch (= its 128-pixel tiles per group: over the

@@ -212,7 +212,9 @@ _SIGS.update({
     "ddl_x6h": [ctypes.POINTER(ConvF32Args), i32, i32, vp],
     "ddl_x6h_ok": [ctypes.POINTER(ConvF32Args), i32, i32],
     "ddl_x6h_slots": [ctypes.POINTER(ConvF32Args), i32],
-    "ddl_x6hw": [ctypes.POINTER(ConvF32Args), vp],
+    "ddl_x6h_residency": [i32, i32, i32, i32, i32],
+    "ddl_x6h_layout": [ctypes.POINTER(ConvF32Args), i32, i32, ctypes.POINTER(ctypes.c_int)],
+    "ddl_x6hw":[ctypes.POINTER(ConvF32Args), vp],
     "ddl_x6hw_ok": [ctypes.POINTER(ConvF32Args)],
     "ddl_x6hw_tiles": [ctypes.POINTER(ConvF32Args)],
     "ddl_convf32_wgrad_reduce": [vp, vp, i64, i32, i64, i32, i32, f32, vp],

@@ -202,6 +202,27 @@ def _x6h_native_ok(mode: int, g) -> bool:
     return r
 
 
+# LDS size classes of the halo kernel's instances (conv_x6h.hip HBTINY / HBSMALL / HBLARGE, bytes of
+# halo image): a BP 64 launch whose halo layout fits HALO_TINY runs three workgroups per CU
+HALO_TINY, HALO_SMALL, HALO_LARGE = 26624, 32768, 45056
+
+
+def halo_layout(mode: int, geom, bp: int = 64):
+    """The halo layout conv_x6h.hip gives this launch (host arithmetic only, no GPU):
+    {ROWB, SEGB, HBYTES, HP, tier} with tier the LDS size class in bytes, or None where the kernel
+    declines the geometry."""
+    out = (ctypes.c_int * 5)()
+    a = _args(geom)
+    if _lib.kernels().ddl_x6h_layout(ctypes.byref(a), mode, cfg_of(bp, 128), out) != 0:
+        return None
+    return dict(zip(("ROWB", "SEGB", "HBYTES", "HP", "tier"), out))
+
+
+def halo_residency(mode: int, bp: int, rs: int, tier: int, padw: bool = False) -> int:
+    """Workgroups per CU of one conv_x6h.hip instance (the HIP occupancy query), -1: no such instance."""
+    return int(_lib.kernels().ddl_x6h_residency(mode, bp, rs, tier, int(padw)))
+
+
 # A stride-1 1x1 conv is a GEMM over pixels: its image shape does not matter. FLAT1X1 re-shapes
 # such a launch as rows of 128 pixels (N = 1, W = 128) whenever N*H*W % 128 == 0 and the image width
 # is not already a power of two (ResNet-50's 56 / 28 / 14 / 7), so the halo kernels
