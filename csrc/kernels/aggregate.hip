@@ -12,41 +12,20 @@
 //                        [north-star, absent in reference].
 //   ddl_coord_select   : coordinate-wise median / trimmed mean over K <= 128 client vectors by an
 //                        in-register bitonic sort per coordinate (Yin et al. 2018) [north-star].
-#include "ddl_common.h"
+#include "quad_stream.h"
 
 __global__ void weighted_sum_kernel(const float* __restrict__ src, long long ld,
                                     const float* __restrict__ coeff, int G, long long n,
                                     float* __restrict__ out, int accumulate) {
-  // every product rounded on its own, then added: hipcc contracts a * b + c into an fma by default
-  // (also through __fmul_rn / __fadd_rn, whose header bodies carry the contract flag), which made the
-  // G-row single-process sum differ from per-rank partials summed across ranks
-#pragma clang fp contract(off)
-  // float4 path only when every row start and the output are 16-B aligned (a sub-slice of a
-  // flat buffer passed as `out` / `src` need not be)
+  // quads only when every row start and the output are 16-B aligned (a sub-slice of a flat buffer
+  // passed as `out` / `src` need not be)
   const bool vec = (ld % 4) == 0 && (((uintptr_t)out | (uintptr_t)src) & 15) == 0;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long e = t * 4;
-    if (e + 4 <= n && vec) {
-      float4 acc = accumulate ? *(const float4*)(out + e) : make_float4(0, 0, 0, 0);
-      // products rounded, then added in client order (no fused multiply-add): the same bits as
-      // clients spread over ranks (each rank's product, then the all-reduce add) for 2 ranks, and
-      // the reference's sum of n_k/n-scaled state dicts (hfl_complete.py:370-378)
-      for (int g = 0; g < G; ++g) {
-        const float c = coeff[g];
-        const float4 v = *(const float4*)(src + g * ld + e);
-        acc.x = acc.x + c * v.x; acc.y = acc.y + c * v.y;  // no contraction: see the pragma
-        acc.z = acc.z + c * v.z; acc.w = acc.w + c * v.w;
-      }
-      *(float4*)(out + e) = acc;
-    } else {
-      for (long long k = e; k < min(n, e + 4); ++k) {
-        float acc = accumulate ? out[k] : 0.f;
-        for (int g = 0; g < G; ++g) acc = acc + coeff[g] * src[g * ld + k];
-        out[k] = acc;
-      }
-    }
-  }
+  quad_stream(n, vec, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    fvec<W> acc = accumulate ? ldv<W>(out + e) : fzero<W>();
+    add_weighted_rows<W>(acc, src, ld, coeff, G, e);  // products rounded, added in client order
+    stv<W>(out + e, acc);
+  });
 }
 
 DDL_API int ddl_weighted_sum(const float* src, long long ld, const float* coeff, int G, long long n,

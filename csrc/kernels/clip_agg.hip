@@ -8,12 +8,13 @@
 //   ddl_clipped_sum   : delta[i] (+)= sum_k cs[k] * fl32(x_ki - c_i), rows with cs[k] == 0 not read
 //   ddl_apply_update  : w[i] = c[i] + delta[i] + std * z_i, z_i ~ N(0, 1) from Philox
 //
-// All four stream: two reads of the client rows (norms, then the sum), 16-B loads where every row
-// start is 16-B aligned (the scalar path otherwise, as weighted_sum_kernel), no LDS tiling, no
-// scratch, no float atomics, and no block waits for another: the per-block partial squared norms
-// go out with plain stores and a tiny second launch folds them in a fixed order, so the norms (and
-// with them the whole aggregate) are bit-reproducible. G is bounded by memory only.
-#include "ddl_common.h"
+// All four stream: two reads of the client rows (norms, then the sum), no LDS tiling, no scratch,
+// no float atomics, and no block waits for another: the per-block partial squared norms go out with
+// plain stores and a tiny second launch folds them in a fixed order, so the norms (and with them
+// the whole aggregate) are bit-reproducible. G is bounded by memory only. The squared norms and the
+// sum run on quad_stream (quad_stream.h): 16-B loads where every row start is 16-B aligned, element
+// by element otherwise, one body for both; apply_update keeps a loop of its own (see there).
+#include "quad_stream.h"
 
 // blocks along a row for the squared norms: about 2048 blocks in all over the G rows (256 CUs x 8
 // resident blocks, the rest by the grid-stride loop). Measured at 8 rows x 11.2M with a centre:
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void update_sqnorm_kernel(const float* __restr
                                                             double* __restrict__ part) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
-  // float4 path only when every row start and the centre are 16-B aligned
+  // quads only when every row start and the centre are 16-B aligned
   const bool vec = (ld % 4) == 0 && (((uintptr_t)X | (uintptr_t)c) & 15) == 0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int g = blockIdx.y; g < G; g += gridDim.y) {
@@ -38,24 +39,17 @@ __global__ __launch_bounds__(256) void update_sqnorm_kernel(const float* __restr
     // the difference rounded to fp32 (the update as `rows - w_global` forms it), its square exact
     // in double and added in double from the first add
     double acc = 0.0;
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-         t += (long long)gridDim.x * blockDim.x) {
-      const long long e = t * 4;
-      if (e + 4 <= n && vec) {
-        const float4 v = *(const float4*)(row + e);
-        const float4 m = c ? *(const float4*)(c + e) : make_float4(0, 0, 0, 0);
-        const float d0 = v.x - m.x, d1 = v.y - m.y, d2 = v.z - m.z, d3 = v.w - m.w;
-        acc += (double)d0 * (double)d0;
-        acc += (double)d1 * (double)d1;
-        acc += (double)d2 * (double)d2;
-        acc += (double)d3 * (double)d3;
-      } else {
-        for (long long k = e; k < min(n, e + 4); ++k) {
-          const float d = row[k] - (c ? c[k] : 0.f);
-          acc += (double)d * (double)d;
-        }
+    quad_stream(n, vec, [&](long long e, auto w) {
+#pragma clang fp contract(off)
+      constexpr int W = decltype(w)::value;
+      const fvec<W> v = ldv<W>(row + e);
+      const fvec<W> m = c ? ldv<W>(c + e) : fzero<W>();
+#pragma unroll
+      for (int i = 0; i < W; ++i) {
+        const float d = v[i] - m[i];
+        acc += (double)d * (double)d;
       }
-    }
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if (lane == 0) red[wid] = acc;
@@ -135,37 +129,23 @@ DDL_API int ddl_clip_scales(const double* sq, const float* coeff, int G, double 
 __global__ void clipped_sum_kernel(const float* __restrict__ X, long long ld, const float* c,
                                    const float* __restrict__ cs, int G, long long n, float* out,
                                    int accumulate) {
-  // difference, product and sum each rounded on their own (no fused multiply-add), rows added in
-  // order: the same bits wherever the rows live, as weighted_sum_kernel
-#pragma clang fp contract(off)
   const bool vec = (ld % 4) == 0 && (((uintptr_t)out | (uintptr_t)X | (uintptr_t)c) & 15) == 0;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long e = t * 4;
-    if (e + 4 <= n && vec) {
-      float4 acc = accumulate ? *(const float4*)(out + e) : make_float4(0, 0, 0, 0);
-      const float4 m = c ? *(const float4*)(c + e) : make_float4(0, 0, 0, 0);
-      for (int g = 0; g < G; ++g) {
-        const float k = cs[g];
-        if (k == 0.f) continue;  // dropped row (or zero weight): not read, 0 * NaN would be NaN
-        const float4 v = *(const float4*)(X + g * ld + e);
-        acc.x = acc.x + k * (v.x - m.x); acc.y = acc.y + k * (v.y - m.y);
-        acc.z = acc.z + k * (v.z - m.z); acc.w = acc.w + k * (v.w - m.w);
-      }
-      *(float4*)(out + e) = acc;
-    } else {
-      for (long long j = e; j < min(n, e + 4); ++j) {
-        float acc = accumulate ? out[j] : 0.f;
-        const float m = c ? c[j] : 0.f;
-        for (int g = 0; g < G; ++g) {
-          const float k = cs[g];
-          if (k == 0.f) continue;
-          acc = acc + k * (X[g * ld + j] - m);
-        }
-        out[j] = acc;
-      }
+  quad_stream(n, vec, [&](long long e, auto w) {
+    // difference, product and sum each rounded on their own (no fused multiply-add), rows added in
+    // order: the same bits wherever the rows live, as weighted_sum_kernel
+#pragma clang fp contract(off)
+    constexpr int W = decltype(w)::value;
+    fvec<W> acc = accumulate ? ldv<W>(out + e) : fzero<W>();
+    const fvec<W> m = c ? ldv<W>(c + e) : fzero<W>();
+    for (int g = 0; g < G; ++g) {
+      const float k = cs[g];
+      if (k == 0.f) continue;  // dropped row (or zero weight): not read, 0 * NaN would be NaN
+      const fvec<W> v = ldv<W>(X + g * ld + e);
+#pragma unroll
+      for (int i = 0; i < W; ++i) acc[i] = acc[i] + k * (v[i] - m[i]);
     }
-  }
+    stv<W>(out + e, acc);
+  });
 }
 
 DDL_API int ddl_clipped_sum(const float* X, long long ld, const float* center, const float* cs, int G,
@@ -197,7 +177,9 @@ __device__ __forceinline__ void normal4(uint2 key, long long q, uint32_t round, 
 // w[j] = (c[j] or 0) + delta[j] + std * z[off + j], j in [0, n). One thread per quad q of the
 // GLOBAL index off + j, so a call on a sub-slice draws what the full call draws; `off` need not be a
 // multiple of 4 (then the scalar path). w may alias c: every thread reads its elements before it
-// writes them. std == 0: exactly c + delta, no RNG work.
+// writes them. std == 0: exactly c + delta, no RNG work. Not on quad_stream: its quads belong to
+// the global index, so the first one may begin before the slice (j0 < 0), which the shared loop
+// over [0, n) has no notion of.
 __global__ void apply_update_kernel(float* w, const float* c, const float* __restrict__ delta, long long n,
                                     long long off, float std, uint2 key, uint32_t round) {
 #pragma clang fp contract(off)

@@ -1,10 +1,16 @@
-// Remedies for client drift under non-IID data [north-star, absent in reference]: the FedProx local
-// step (Li et al. 2020) and the FedOpt server optimizers (Reddi et al. 2021, Algorithm 2; FedAvgM
-// of Hsu et al. 2019).
+// Remedies for client drift under non-IID data [north-star, absent in reference]: the corrected
+// local step of FedProx (Li et al. 2020) and SCAFFOLD (Karimireddy et al. 2020), and the FedOpt
+// server optimizers (Reddi et al. 2021, Algorithm 2; FedAvgM of Hsu et al. 2019).
 //
-//   ddl_sgd_prox        : rows p/g/mom/shadow [G][P], one anchor a [P] (the round's w_global):
-//                         d = g * grad_scale + wd * p + mu * (p - a[col]), then momentum / dampening /
-//                         nesterov as sgd_kernel, p -= lr * d, bf16 shadow refreshed in the same pass
+//   ddl_sgd_corrected   : rows p/g/mom/shadow [G][P]: d = g * grad_scale + wd * p, d = d + term, then
+//                         momentum / dampening / nesterov as sgd_kernel, p -= lr * d, bf16 shadow
+//                         refreshed in the same pass. One kernel template, an instance per term:
+//                           SGD_PROX    : mu * (p - ref[col]), ref the anchor [P] (the round's w_global)
+//                           SGD_CONTROL : ref[col] - bank[slot_client[row]][col], ref the server's control
+//                                         variate c [P], client i's in row i of bank [N][ld], read in
+//                                         place through the int32 device table slot_client [G] (so a
+//                                         captured round graph keeps its pointers and the next round
+//                                         only overwrites the table's contents)
 //   ddl_server_opt      : delta = x_is_delta ? x : x - w, then in place on w, m, v [n]
 //                           sgdm    : m = b1 * m + delta                   w = w + lr * m
 //                           adagrad : m = b1 * m + (1 - b1) * delta        v = v + delta * delta
@@ -18,79 +24,103 @@
 //                         moving (G + 6) n floats in one launch instead of (G + 8) n in two
 //                         (G + 4 against G + 6 for sgdm, which has no v)
 //
-// All three stream: grid-stride, 256 threads, 16-B accesses where every base pointer and row stride
-// is 16-B aligned (the scalar path otherwise, the same bits), every add, multiply, divide and sqrtf
-// rounded on its own (no contraction), no LDS, no atomics, no scratch.
-#include "ddl_common.h"
+// All three stream on quad_stream (quad_stream.h): grid-stride, 256 threads, 16-B accesses where
+// every base pointer and row stride is 16-B aligned, element by element otherwise, one body for
+// both; every add, multiply, divide and sqrtf rounded on its own (no contraction), no LDS, no
+// atomics, no scratch.
+#include "quad_stream.h"
 
-struct SGDProxArgs {
-  float* p; const float* g; float* mom; bf16_t* shadow; const float* anchor;
-  long long rows, P;
+enum { SGD_PROX = 0, SGD_CONTROL = 1 };
+
+struct SGDCorrectedArgs {
+  float* p; const float* g; float* mom; bf16_t* shadow;
+  const float* ref;                             // [P]: the anchor (SGD_PROX), the server's c (SGD_CONTROL)
+  const float* bank; const int* slot_client;    // SGD_CONTROL: clients' rows [N][ld], slot -> client
+  long long rows, P, ld;
   float lr, wd, momentum, dampening, grad_scale, mu;
-  int nesterov, first_step;
+  int nesterov, first_step, correction;
 };
 
-__device__ __forceinline__ float prox_update(const SGDProxArgs& a, float p, float g, float anc, float& m) {
+// The correction terms: what the step adds to d for the elements [col, col + W) of slot `row`, and
+// what has to be aligned beyond p, g, mom and P for the 16-B path.
+struct ProxTerm {  // mu * (p - anchor[col])
+  static __device__ __forceinline__ bool aligned(const SGDCorrectedArgs& a) { return ((uintptr_t)a.ref & 15) == 0; }
+  template <int W>
+  static __device__ __forceinline__ fvec<W> term(const SGDCorrectedArgs& a, long long, long long col, const fvec<W>& p) {
 #pragma clang fp contract(off)
-  float d = g * a.grad_scale + a.wd * p;
-  d = d + a.mu * (p - anc);
-  if (a.momentum != 0.f) {
-    m = a.first_step ? d : a.momentum * m + (1.f - a.dampening) * d;
-    d = a.nesterov ? d + a.momentum * m : m;
+    const fvec<W> anc = ldv<W>(a.ref + col);
+    fvec<W> t;
+#pragma unroll
+    for (int i = 0; i < W; ++i) t[i] = a.mu * (p[i] - anc[i]);
+    return t;
   }
-  return p - a.lr * d;
-}
+};
 
-__global__ __launch_bounds__(256) void sgd_prox_kernel(SGDProxArgs a) {
+struct ControlTerm {  // c[col] - bank[slot_client[row]][col]
+  static __device__ __forceinline__ bool aligned(const SGDCorrectedArgs& a) {
+    return (a.ld % 4) == 0 && (((uintptr_t)a.ref | (uintptr_t)a.bank) & 15) == 0;
+  }
+  template <int W>
+  static __device__ __forceinline__ fvec<W> term(const SGDCorrectedArgs& a, long long row, long long col, const fvec<W>&) {
 #pragma clang fp contract(off)
+    const fvec<W> c = ldv<W>(a.ref + col);
+    const fvec<W> ci = ldv<W>(a.bank + (long long)a.slot_client[row] * a.ld + col);
+    fvec<W> t;
+#pragma unroll
+    for (int i = 0; i < W; ++i) t[i] = c[i] - ci[i];
+    return t;
+  }
+};
+
+template <class Term>
+__global__ __launch_bounds__(256) void sgd_corrected_kernel(SGDCorrectedArgs a) {
   const long long n = a.rows * a.P;
   const bool has_mom = a.mom && a.momentum != 0.f;
   const bool ld_mom = has_mom && !a.first_step;
-  // 16-B path only when no quad straddles a row and every base is aligned (the shadow's 8-B store too)
-  const bool vec = (a.P % 4) == 0 &&
-                   (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.mom | (uintptr_t)a.anchor) & 15) == 0 &&
-                   ((uintptr_t)a.shadow & 7) == 0;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long e = t * 4;
-    if (vec) {  // P % 4 == 0: n % 4 == 0, the quad is whole and lies in one row
-      const long long col = e % a.P;
-      float4 pv = *(const float4*)(a.p + e);
-      const float4 gv = *(const float4*)(a.g + e);
-      const float4 av = *(const float4*)(a.anchor + col);
-      float4 mv = ld_mom ? *(const float4*)(a.mom + e) : make_float4(0, 0, 0, 0);
-      pv.x = prox_update(a, pv.x, gv.x, av.x, mv.x);
-      pv.y = prox_update(a, pv.y, gv.y, av.y, mv.y);
-      pv.z = prox_update(a, pv.z, gv.z, av.z, mv.z);
-      pv.w = prox_update(a, pv.w, gv.w, av.w, mv.w);
-      *(float4*)(a.p + e) = pv;
-      if (has_mom) *(float4*)(a.mom + e) = mv;
-      if (a.shadow) {
-        i2v o;
-        o[0] = (int)pack_bf2(pv.x, pv.y);
-        o[1] = (int)pack_bf2(pv.z, pv.w);
-        *(i2v*)(a.shadow + e) = o;
+  // 16-B path only when no quad straddles a row (P % 4 == 0: n % 4 == 0, every quad is whole and
+  // lies in one row) and every base is aligned (the shadow's 8-B store too)
+  const bool vec = (a.P % 4) == 0 && (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.mom) & 15) == 0 &&
+                   ((uintptr_t)a.shadow & 7) == 0 && Term::aligned(a);
+  quad_stream(n, vec, [&](long long e, auto w) {
+#pragma clang fp contract(off)
+    constexpr int W = decltype(w)::value;
+    const long long row = e / a.P, col = e - row * a.P;
+    fvec<W> p = ldv<W>(a.p + e);
+    const fvec<W> g = ldv<W>(a.g + e);
+    const fvec<W> t = Term::template term<W>(a, row, col, p);
+    fvec<W> m = ld_mom ? ldv<W>(a.mom + e) : fzero<W>();
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+      float d = g[i] * a.grad_scale + a.wd * p[i];
+      d = d + t[i];
+      if (a.momentum != 0.f) {
+        m[i] = a.first_step ? d : a.momentum * m[i] + (1.f - a.dampening) * d;
+        d = a.nesterov ? d + a.momentum * m[i] : m[i];
       }
-    } else {
-      for (long long k = e; k < min(n, e + 4); ++k) {
-        float m = ld_mom ? a.mom[k] : 0.f;
-        const float p = prox_update(a, a.p[k], a.g[k], a.anchor[k % a.P], m);
-        a.p[k] = p;
-        if (has_mom) a.mom[k] = m;
-        if (a.shadow) a.shadow[k] = f2bf(p);
-      }
+      p[i] = p[i] - a.lr * d;
     }
-  }
+    stv<W>(a.p + e, p);
+    if (has_mom) stv<W>(a.mom + e, m);
+    if (a.shadow) stv_bf16<W>(a.shadow + e, p);
+  });
 }
 
-DDL_API int ddl_sgd_prox(const SGDProxArgs* a, hipStream_t s) {
-  if (a->rows < 1 || a->P < 1 || !a->p || !a->g || !a->anchor) return (int)hipErrorInvalidValue;
+DDL_API int ddl_sgd_corrected(const SGDCorrectedArgs* a, hipStream_t s) {
+  if (a->rows < 1 || a->P < 1 || !a->p || !a->g || !a->ref) return (int)hipErrorInvalidValue;
   if (a->momentum != 0.f && !a->mom) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(sgd_prox_kernel, dim3(grid_for((a->rows * a->P + 3) / 4, 256)), dim3(256), 0, s, *a);
+  const dim3 grid(grid_for((a->rows * a->P + 3) / 4, 256));
+  if (a->correction == SGD_PROX) {
+    hipLaunchKernelGGL(sgd_corrected_kernel<ProxTerm>, grid, dim3(256), 0, s, *a);
+  } else if (a->correction == SGD_CONTROL) {
+    if (!a->bank || !a->slot_client || a->ld < a->P) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sgd_corrected_kernel<ControlTerm>, grid, dim3(256), 0, s, *a);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }
 
-DDL_API int ddl_sgd_prox_args_size() { return (int)sizeof(SGDProxArgs); }
+DDL_API int ddl_sgd_corrected_args_size() { return (int)sizeof(SGDCorrectedArgs); }
 
 // ------------------------------------------------------------------------------ server optimizers
 enum { SOPT_SGDM = 0, SOPT_ADAGRAD = 1, SOPT_ADAM = 2, SOPT_YOGI = 3 };
@@ -100,16 +130,16 @@ struct ServerOptHyper {
   int kind, x_is_delta;
 };
 
-// One coordinate, every operation rounded on its own in the order of the header comment. Returns
-// false (w, m, v untouched) for a NaN / Inf delta.
-__device__ __forceinline__ bool server_update(const ServerOptHyper& h, float x, float& w, float& m, float& v) {
+// One coordinate, every operation rounded on its own in the order of the header comment; a NaN /
+// Inf delta leaves w, m, v untouched.
+__device__ __forceinline__ void server_update(const ServerOptHyper& h, float x, float& w, float& m, float& v) {
 #pragma clang fp contract(off)
   const float d = h.x_is_delta ? x : x - w;
-  if ((__float_as_uint(d) & 0x7f800000u) == 0x7f800000u) return false;
+  if ((__float_as_uint(d) & 0x7f800000u) == 0x7f800000u) return;
   if (h.kind == SOPT_SGDM) {
     m = h.beta1 * m + d;
     w = w + h.lr * m;
-    return true;
+    return;
   }
   const float omb1 = 1.f - h.beta1, omb2 = 1.f - h.beta2;
   m = h.beta1 * m + omb1 * d;
@@ -124,81 +154,45 @@ __device__ __forceinline__ bool server_update(const ServerOptHyper& h, float x, 
     v = v - omb2 * d2 * sgn;
   }
   w = w + h.lr * m / (sqrtf(v) + h.tau);
-  return true;
 }
 
-// the quad's state, loaded by the caller (before its row loop, so the loads are in flight with it)
-__device__ __forceinline__ void server_update4(const ServerOptHyper& h, const float4& x, float4 wv, float4 mv,
-                                               float4 vv, float* w, float* m, float* v, long long e) {
-  const bool has_v = h.kind != SOPT_SGDM;
-  // a skipped coordinate stores back the bits it loaded
-  server_update(h, x.x, wv.x, mv.x, vv.x);
-  server_update(h, x.y, wv.y, mv.y, vv.y);
-  server_update(h, x.z, wv.z, mv.z, vv.z);
-  server_update(h, x.w, wv.w, mv.w, vv.w);
-  *(float4*)(w + e) = wv;
-  *(float4*)(m + e) = mv;
-  if (has_v) *(float4*)(v + e) = vv;
-}
-
-__device__ __forceinline__ void server_update1(const ServerOptHyper& h, float x, float* w, float* m, float* v,
-                                               long long k) {
-  const bool has_v = h.kind != SOPT_SGDM;
-  float wk = w[k], mk = m[k], vk = has_v ? v[k] : 0.f;
-  if (server_update(h, x, wk, mk, vk)) {
-    w[k] = wk;
-    m[k] = mk;
-    if (has_v) v[k] = vk;
-  }
+// The step on W coordinates whose state the caller loaded (before its row loop, so the loads are in
+// flight with it); a skipped coordinate stores back the bits it loaded.
+template <int W>
+__device__ __forceinline__ void server_step(const ServerOptHyper& h, const fvec<W>& x, fvec<W> wv, fvec<W> mv,
+                                            fvec<W> vv, float* w, float* m, float* v, long long e) {
+#pragma unroll
+  for (int i = 0; i < W; ++i) server_update(h, x[i], wv[i], mv[i], vv[i]);
+  stv<W>(w + e, wv);
+  stv<W>(m + e, mv);
+  if (h.kind != SOPT_SGDM) stv<W>(v + e, vv);
 }
 
 // x may alias nothing it writes: w, m, v are read before they are written by the same thread
 __global__ __launch_bounds__(256) void server_opt_kernel(float* w, const float* __restrict__ x, float* m, float* v,
                                                          long long n, ServerOptHyper h) {
-#pragma clang fp contract(off)
   const bool vec = (((uintptr_t)w | (uintptr_t)x | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long e = t * 4;
-    if (e + 4 <= n && vec) {
-      const float4 wv = *(const float4*)(w + e), mv = *(const float4*)(m + e);
-      const float4 vv = v ? *(const float4*)(v + e) : make_float4(0, 0, 0, 0);
-      server_update4(h, *(const float4*)(x + e), wv, mv, vv, w, m, v, e);
-    } else {
-      for (long long k = e; k < min(n, e + 4); ++k) server_update1(h, x[k], w, m, v, k);
-    }
-  }
+  quad_stream(n, vec, [&](long long e, auto wd) {
+    constexpr int W = decltype(wd)::value;
+    const fvec<W> wv = ldv<W>(w + e), mv = ldv<W>(m + e);
+    const fvec<W> vv = v ? ldv<W>(v + e) : fzero<W>();
+    server_step<W>(h, ldv<W>(x + e), wv, mv, vv, w, m, v, e);
+  });
 }
 
 __global__ __launch_bounds__(256) void server_opt_rows_kernel(const float* __restrict__ rows, long long ld,
                                                               const float* __restrict__ coeff, int G, float* w,
                                                               float* m, float* v, long long n, ServerOptHyper h) {
-#pragma clang fp contract(off)
   const bool vec = (ld % 4) == 0 &&
                    (((uintptr_t)rows | (uintptr_t)w | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t * 4 < n;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long e = t * 4;
-    if (e + 4 <= n && vec) {
-      const float4 wv = *(const float4*)(w + e), mv = *(const float4*)(m + e);
-      const float4 vv = v ? *(const float4*)(v + e) : make_float4(0, 0, 0, 0);
-      // weighted_sum_kernel's sum: from 0, products rounded, added in client order
-      float4 acc = make_float4(0, 0, 0, 0);
-      for (int g = 0; g < G; ++g) {
-        const float c = coeff[g];
-        const float4 r = *(const float4*)(rows + g * ld + e);
-        acc.x = acc.x + c * r.x; acc.y = acc.y + c * r.y;
-        acc.z = acc.z + c * r.z; acc.w = acc.w + c * r.w;
-      }
-      server_update4(h, acc, wv, mv, vv, w, m, v, e);
-    } else {
-      for (long long k = e; k < min(n, e + 4); ++k) {
-        float acc = 0.f;
-        for (int g = 0; g < G; ++g) acc = acc + coeff[g] * rows[g * ld + k];
-        server_update1(h, acc, w, m, v, k);
-      }
-    }
-  }
+  quad_stream(n, vec, [&](long long e, auto wd) {
+    constexpr int W = decltype(wd)::value;
+    const fvec<W> wv = ldv<W>(w + e), mv = ldv<W>(m + e);
+    const fvec<W> vv = v ? ldv<W>(v + e) : fzero<W>();
+    fvec<W> acc = fzero<W>();  // weighted_sum_kernel's sum, from 0
+    add_weighted_rows<W>(acc, rows, ld, coeff, G, e);
+    server_step<W>(h, acc, wv, mv, vv, w, m, v, e);
+  });
 }
 
 static bool server_opt_args_ok(const float* w, const float* m, const float* v, long long n, int kind, float lr,

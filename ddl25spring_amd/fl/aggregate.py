@@ -273,6 +273,36 @@ class Krum(_Sharded):
         return [] if self._sel is None else self._sel.tolist()
 
 
+def aggregate_into(agg, ctx, rows, coeffs, out, *, center, counts, keys, as_update: bool = False) -> bool:
+    """The one place that knows the aggregators' three calling conventions. rows [G_local, P] are
+    the clients' vectors and ``center`` [P] what their updates are taken against (None: the rows
+    are the updates already, FedSGD's gradients); counts / keys: the clients per rank and each
+    rank-major row's global order (``_Sharded``, ``Krum``). The result goes to out [P]: the new
+    vector (``center`` + the aggregate update), or with ``as_update`` what the rule itself forms
+    without another rounding -- the robust rules' aggregate *update* (``(center + agg) - center``
+    is not ``agg`` in fp32), the means' new vector. -> True when out holds an update.
+
+      mean          agg(ctx, rows, coeffs, out)
+      takes_center  agg(ctx, rows, coeffs, out, center=, counts=): the clipped mean forms the
+                    updates, clips, averages and adds the centre back itself
+      needs_all     agg(ctx, updates, counts, P, keys=) -> the aggregate update. The robust rules
+                    act on updates; the new vector is added in place, so it needs ``out is center``"""
+    if getattr(agg, "takes_center", False):
+        agg(ctx, rows, coeffs, out, center=center, counts=counts)
+        return False
+    if not getattr(agg, "needs_all", False):
+        agg(ctx, rows, coeffs, out)
+        return False
+    upd = rows if center is None else rows - center
+    res = agg(ctx, upd, counts, out.numel(), keys=keys)
+    if center is None or as_update:
+        out.copy_(res)
+        return True
+    assert out is center, "a robust rule's update is added to the centre in place"
+    out.add_(res)
+    return False
+
+
 def make_aggregator(name: str, **kw):
     name = name.lower()
     if name in ("mean", "fedavg", "avg"):

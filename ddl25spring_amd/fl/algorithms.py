@@ -21,7 +21,7 @@ import torch
 from ..ops import functional as Fn
 from ..runtime import dist as rdist
 from ..utils.metrics import PhaseTimer
-from .aggregate import MeanAggregator, make_aggregator
+from .aggregate import MeanAggregator, aggregate_into, make_aggregator
 from .local import LocalTrainer
 from .result import RunResult
 from .server_opt import make_server_opt
@@ -146,15 +146,20 @@ class FederatedBase:
             sd["server_opt"] = self.server_opt.state_dict()
         return sd
 
+    def _layout_fix(self, sd: dict):
+        """-> the map of a checkpoint's flat row [P] (or rows [N, P]) to this run's parameter
+        layout: by parameter name when the writer used another layout, else the identity."""
+        st = self.net.store
+        src = sd.get("param_layout") or st.param_layout()
+        if [list(x) for x in src] == st.param_layout():
+            return lambda t: t
+        return lambda t: st.remap_flat(t, src) if t.dim() == 1 else torch.stack([st.remap_flat(r, src) for r in t])
+
     def load_state_dict(self, sd: dict) -> None:
         if (sd["algorithm"], sd["N"], sd["K"]) != (self.algorithm, self.N, self.K):
             raise ValueError("checkpoint is for a different federation "
                              f"{(sd['algorithm'], sd['N'], sd['K'])}")
-        # flat rows are remapped by parameter name when the writer used another layout
-        st = self.net.store
-        src = sd.get("param_layout") or st.param_layout()
-        fix = (lambda t: t) if [list(x) for x in src] == st.param_layout() else \
-            (lambda t: st.remap_flat(t, src))
+        fix = self._layout_fix(sd)
         self.w_global.copy_(fix(sd["w_global"]).to(self.dev))
         self.b_global.copy_(sd["b_global"].to(self.dev))
         if "g_global" in sd and hasattr(self, "g_global"):
@@ -330,15 +335,8 @@ class FedAvg(FederatedBase):
     def _aggregate(self, rows, coeffs, counts):
         if self.server_opt is not None:
             return self._aggregate_server_opt(rows, coeffs, counts)
-        if getattr(self.aggregator, "takes_center", False):
-            # clipped mean: updates against w_global, clipped, averaged and added back in place
-            self.aggregator(self.ctx, rows, coeffs, self.w_global, center=self.w_global, counts=counts)
-        elif not getattr(self.aggregator, "needs_all", False):
-            self.aggregator(self.ctx, rows, coeffs, self.w_global)
-        else:
-            upd = rows - self.w_global  # robust rules act on updates
-            agg = self.aggregator(self.ctx, upd, counts, self.w_global.numel(), keys=self._row_keys(counts))
-            self.w_global.add_(agg)
+        aggregate_into(self.aggregator, self.ctx, rows, coeffs, self.w_global, center=self.w_global,
+                       counts=counts, keys=self._row_keys(counts))
 
     # one launch for sum + server step where the plain mean needs no cross-rank route (off: the
     # scratch-row route, which the tests hold bit-equal to it)
@@ -357,16 +355,10 @@ class FedAvg(FederatedBase):
         target = getattr(self, "_opt_target", None)
         if target is None:
             target = self._opt_target = torch.empty_like(self.w_global)
-        if getattr(agg, "takes_center", False):  # clipped mean: target = w_global + clipped update
-            agg(self.ctx, rows, coeffs, target, center=self.w_global, counts=counts)
-            opt.step(self.w_global, target, False)
-        elif not getattr(agg, "needs_all", False):
-            agg(self.ctx, rows, coeffs, target)
-            opt.step(self.w_global, target, False)
-        else:  # robust rules act on updates: their result already is the delta
-            upd = rows - self.w_global
-            target.copy_(agg(self.ctx, upd, counts, self.w_global.numel(), keys=self._row_keys(counts)))
-            opt.step(self.w_global, target, True)
+        # a robust rule's result already is the delta; a mean's is the new vector
+        is_delta = aggregate_into(agg, self.ctx, rows, coeffs, target, center=self.w_global, counts=counts,
+                                  keys=self._row_keys(counts), as_update=True)
+        opt.step(self.w_global, target, is_delta)
 
 
 class Scaffold(FedAvg):
@@ -476,15 +468,12 @@ class Scaffold(FedAvg):
 
     def load_state_dict(self, sd: dict) -> None:
         super().load_state_dict(sd)
-        st = self.net.store
-        src = sd.get("param_layout") or st.param_layout()
-        same = [list(x) for x in src] == st.param_layout()
-        fix = (lambda t: t) if same else (lambda t: st.remap_flat(t, src))
+        fix = self._layout_fix(sd)
         self.c_global.copy_(fix(sd["c_global"]).to(self.dev))
         bank = sd["c_bank"]
         if bank.shape[0] != self.N:
             raise ValueError(f"checkpoint holds {bank.shape[0]} control variates, this federation has {self.N} clients")
-        self.c_bank.copy_((bank if same else torch.stack([fix(r) for r in bank])).to(self.dev))
+        self.c_bank.copy_(fix(bank).to(self.dev))
 
 
 class FedSGD(FederatedBase):
@@ -538,13 +527,8 @@ class FedSGD(FederatedBase):
             self.attack.poison_updates(st.grad[:G], torch.zeros_like(self.w_global), mine)
         coeffs = torch.tensor([self.counts[c] / total for c in mine], dtype=torch.float32,
                               device=self.dev)
-        if getattr(self.aggregator, "takes_center", False):  # the updates are the gradients
-            self.aggregator(self.ctx, st.grad[:G], coeffs, self.g_global, center=None, counts=counts)
-        elif not getattr(self.aggregator, "needs_all", False):
-            self.aggregator(self.ctx, st.grad[:G], coeffs, self.g_global)
-        else:
-            self.g_global.copy_(self.aggregator(self.ctx, st.grad[:G], counts, self.w_global.numel(),
-                                                keys=self._row_keys(counts)))
+        aggregate_into(self.aggregator, self.ctx, st.grad[:G], coeffs, self.g_global, center=None,  # the updates
+                       counts=counts, keys=self._row_keys(counts))                                  # are the gradients
         # server SGD step (no momentum, as the reference's SGD(lr))
         self.w_global.add_(self.g_global, alpha=-self.lr)
         if G:  # BN running stats from this round's forward passes

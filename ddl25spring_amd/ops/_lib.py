@@ -109,17 +109,14 @@ class SGDDirectArgs(ctypes.Structure):
                 ("lr", f32), ("grad_scale", f32)]
 
 
-class SGDProxArgs(ctypes.Structure):  # fedopt.hip
-    _fields_ = [("p", vp), ("g", vp), ("mom", vp), ("shadow", vp), ("anchor", vp), ("rows", i64),
-                ("P", i64), ("lr", f32), ("wd", f32), ("momentum", f32), ("dampening", f32),
-                ("grad_scale", f32), ("mu", f32), ("nesterov", i32), ("first_step", i32)]
-
-
-class SGDScaffoldArgs(ctypes.Structure):  # scaffold.hip
-    _fields_ = [("p", vp), ("g", vp), ("mom", vp), ("shadow", vp), ("c", vp), ("bank", vp),
+class SGDCorrectedArgs(ctypes.Structure):  # fedopt.hip
+    _fields_ = [("p", vp), ("g", vp), ("mom", vp), ("shadow", vp), ("ref", vp), ("bank", vp),
                 ("slot_client", vp), ("rows", i64), ("P", i64), ("ld", i64), ("lr", f32), ("wd", f32),
-                ("momentum", f32), ("dampening", f32), ("grad_scale", f32), ("nesterov", i32),
-                ("first_step", i32)]
+                ("momentum", f32), ("dampening", f32), ("grad_scale", f32), ("mu", f32),
+                ("nesterov", i32), ("first_step", i32), ("correction", i32)]
+
+
+SGD_PROX, SGD_CONTROL = 0, 1  # SGDCorrectedArgs.correction
 
 
 class AdamArgs(ctypes.Structure):
@@ -190,11 +187,10 @@ _SIGS = {
     "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
     "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
     # fedopt.hip
-    "ddl_sgd_prox": [ctypes.POINTER(SGDProxArgs), vp],
+    "ddl_sgd_corrected": [ctypes.POINTER(SGDCorrectedArgs), vp],
     "ddl_server_opt": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     "ddl_server_opt_rows": [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     # scaffold.hip
-    "ddl_sgd_scaffold": [ctypes.POINTER(SGDScaffoldArgs), vp],
     "ddl_scaffold_finish": [vp, i64, vp, vp, vp, i64, vp, vp, i32, f32, vp, i64, i32, vp],
 }
 
@@ -284,8 +280,7 @@ def kernels():
                                    ("SGDArgs", "ddl_sgd_args_size", SGDArgs),
                                    ("SGDDirectArgs", "ddl_sgd_direct_args_size", SGDDirectArgs),
                                    ("AdamArgs", "ddl_adam_args_size", AdamArgs),
-                                   ("SGDProxArgs", "ddl_sgd_prox_args_size", SGDProxArgs),
-                                   ("SGDScaffoldArgs", "ddl_sgd_scaffold_args_size", SGDScaffoldArgs),
+                                   ("SGDCorrectedArgs", "ddl_sgd_corrected_args_size", SGDCorrectedArgs),
                                    ("ConvF32Args", "ddl_convf32_args_size", ConvF32Args),
                                    ("BNFArgs", "ddl_bnf_args_size", BNFArgs),
                                    ("BNFBwdArgs", "ddl_bnf_bwd_args_size", BNFBwdArgs),

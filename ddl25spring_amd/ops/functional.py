@@ -1221,29 +1221,40 @@ def sgd_direct_step(p, g, shadow, dmap, lr: float, grad_scale: float = 1.0):
     check(_lib.kernels().ddl_sgd_direct(ctypes.byref(a), stream()), "sgd_direct")
 
 
-def sgd_prox_step(p, g, mom, shadow, anchor, lr, mu, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False,
-                  first_step=False, grad_scale=1.0):
-    """The FedProx local step (Li et al. 2020) over contiguous rows p/g/mom/shadow [G, P] with one
-    anchor [P] (the round's w_global): ``d = g * grad_scale + wd * p + mu * (p - anchor)``, momentum
-    / dampening / nesterov as ``sgd_step``, ``p -= lr * d``, shadow refreshed. One launch."""
-    assert p.dim() == 2 and p.shape == g.shape and anchor.numel() == p.shape[1]
+def _sgd_corrected_step(name, correction, term, p, g, mom, shadow, ref_row, lr, wd, momentum, dampening,
+                        nesterov, first_step, grad_scale, mu=0.0, bank=None, slot_client=None):
+    """The corrected local step (fedopt.hip ``ddl_sgd_corrected``) over contiguous rows p/g/mom/shadow
+    [G, P]: ``d = g * grad_scale + wd * p + term``, momentum / dampening / nesterov as ``sgd_step``,
+    ``p -= lr * d``, shadow refreshed. One launch. ``term()`` forms the correction in torch for rows
+    that live on the host."""
+    assert p.dim() == 2 and p.shape == g.shape and ref_row.numel() == p.shape[1]
+    if momentum != 0.0 and mom is None:
+        raise ValueError(f"{name}: momentum needs a momentum buffer")
     if not p.is_cuda:
-        ref.sgd_prox(p, g, mom, shadow, anchor.reshape(1, -1), lr, wd, momentum, dampening, nesterov,
-                     first_step, grad_scale, mu)
+        ref.sgd_corrected(p, g, mom, shadow, term(), lr, wd, momentum, dampening, nesterov, first_step, grad_scale)
         return
-    assert p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and anchor.is_contiguous()
+    assert p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and ref_row.is_contiguous()
     assert mom is None or (mom.is_contiguous() and mom.shape == p.shape)
     assert shadow is None or (shadow.is_contiguous() and shadow.shape == p.shape)
-    if momentum != 0.0 and mom is None:
-        raise ValueError("sgd_prox_step: momentum needs a momentum buffer")
     if p.numel() == 0:
         return
-    a = _lib.SGDProxArgs()
-    a.p, a.g, a.mom, a.shadow, a.anchor = ptr(p), ptr(g), ptr(mom), ptr(shadow), ptr(anchor)
+    a = _lib.SGDCorrectedArgs()
+    a.p, a.g, a.mom, a.shadow = ptr(p), ptr(g), ptr(mom), ptr(shadow)
+    a.ref, a.bank, a.slot_client = ptr(ref_row), ptr(bank), ptr(slot_client)
     a.rows, a.P = p.shape
+    a.ld = p.shape[1] if bank is None or bank.shape[0] <= 1 else bank.stride(0)
     a.lr, a.wd, a.momentum, a.dampening, a.grad_scale, a.mu = lr, wd, momentum, dampening, grad_scale, mu
-    a.nesterov, a.first_step = int(nesterov), int(first_step)
-    check(_lib.kernels().ddl_sgd_prox(ctypes.byref(a), stream()), "sgd_prox")
+    a.nesterov, a.first_step, a.correction = int(nesterov), int(first_step), correction
+    check(_lib.kernels().ddl_sgd_corrected(ctypes.byref(a), stream()), name)
+
+
+def sgd_prox_step(p, g, mom, shadow, anchor, lr, mu, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False,
+                  first_step=False, grad_scale=1.0):
+    """The FedProx local step (Li et al. 2020): the correction is ``mu * (p - anchor)`` with one
+    anchor [P] (the round's w_global) for every row."""
+    _sgd_corrected_step("sgd_prox_step", _lib.SGD_PROX, lambda: ref._s32(mu) * (p - anchor.reshape(1, -1)),
+                        p, g, mom, shadow, anchor, lr, wd, momentum, dampening, nesterov, first_step, grad_scale,
+                        mu=mu)
 
 
 def check_slot_clients(ids, n_clients: int):
@@ -1272,32 +1283,15 @@ def _scaffold_bank_check(name, P, c, bank, slot_client, G):
 
 def sgd_scaffold_step(p, g, mom, shadow, c, bank, slot_client, lr, wd=0.0, momentum=0.0, dampening=0.0,
                       nesterov=False, first_step=False, grad_scale=1.0):
-    """The SCAFFOLD local step (Karimireddy et al. 2020) over contiguous rows p/g/mom/shadow [G, P]:
-    ``d = g * grad_scale + wd * p + (c - bank[slot_client[row]])`` with the server control variate
-    c [P] and the clients' control variates bank [N, P] (rows may be strided), read in place through
-    the int32 table slot_client [G] on the rows' device; momentum / dampening / nesterov as
-    ``sgd_step``, ``p -= lr * d``, shadow refreshed. One launch."""
-    assert p.dim() == 2 and p.shape == g.shape
+    """The SCAFFOLD local step (Karimireddy et al. 2020): the correction is
+    ``c - bank[slot_client[row]]`` with the server control variate c [P] and the clients' control
+    variates bank [N, P] (rows may be strided), read in place through the int32 table slot_client
+    [G] on the rows' device."""
+    assert p.dim() == 2
     _scaffold_bank_check("sgd_scaffold_step", p.shape[1], c, bank, slot_client, p.shape[0])
-    if momentum != 0.0 and mom is None:
-        raise ValueError("sgd_scaffold_step: momentum needs a momentum buffer")
-    if not p.is_cuda:
-        ref.sgd_scaffold(p, g, mom, shadow, c, bank, slot_client, lr, wd, momentum, dampening, nesterov,
-                         first_step, grad_scale)
-        return
-    assert p.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
-    assert mom is None or (mom.is_contiguous() and mom.shape == p.shape)
-    assert shadow is None or (shadow.is_contiguous() and shadow.shape == p.shape)
-    if p.numel() == 0:
-        return
-    a = _lib.SGDScaffoldArgs()
-    a.p, a.g, a.mom, a.shadow = ptr(p), ptr(g), ptr(mom), ptr(shadow)
-    a.c, a.bank, a.slot_client = ptr(c), ptr(bank), ptr(slot_client)
-    a.rows, a.P = p.shape
-    a.ld = bank.stride(0) if bank.shape[0] > 1 else p.shape[1]
-    a.lr, a.wd, a.momentum, a.dampening, a.grad_scale = lr, wd, momentum, dampening, grad_scale
-    a.nesterov, a.first_step = int(nesterov), int(first_step)
-    check(_lib.kernels().ddl_sgd_scaffold(ctypes.byref(a), stream()), "sgd_scaffold")
+    _sgd_corrected_step("sgd_scaffold_step", _lib.SGD_CONTROL, lambda: c.reshape(1, -1) - bank[slot_client.long()],
+                        p, g, mom, shadow, c, lr, wd, momentum, dampening, nesterov, first_step, grad_scale,
+                        bank=bank, slot_client=slot_client)
 
 
 def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c=False):

@@ -410,13 +410,13 @@ def _s32(x):
     return torch.tensor(float(x), dtype=torch.float32)
 
 
-def sgd_prox(p, g, mom, shadow, anchor, lr, wd, momentum, dampening, nesterov, first_step, grad_scale=1.0,
-             mu=0.0):
-    """Rows p/g/mom/shadow [G, P], anchor [P]: every operation a separate fp32 rounding, in
-    sgd_prox_kernel's order."""
-    lr, wd, mo, gs, mu = (_s32(v) for v in (lr, wd, momentum, grad_scale, mu))
+def sgd_corrected(p, g, mom, shadow, term, lr, wd, momentum, dampening, nesterov, first_step, grad_scale=1.0):
+    """Rows p/g/mom/shadow [G, P] and the correction term (broadcastable to them: FedProx's
+    ``mu * (p - anchor)``, SCAFFOLD's ``c - bank[slot_client]``): every operation a separate fp32
+    rounding, in sgd_corrected_kernel's order."""
+    lr, wd, mo, gs = (_s32(v) for v in (lr, wd, momentum, grad_scale))
     d = g * gs + wd * p
-    d = d + mu * (p - anchor)
+    d = d + term
     if momentum != 0:
         if first_step:
             mom.copy_(d)
@@ -464,24 +464,6 @@ def server_opt_rows(rows, coeff, w, m, v, kind, x_is_delta, lr, beta1, beta2, ta
 
 
 # ------------------------------------------------------- SCAFFOLD (scaffold.hip), fp32 torch twins
-def sgd_scaffold(p, g, mom, shadow, c, bank, slot_client, lr, wd, momentum, dampening, nesterov, first_step,
-                 grad_scale=1.0):
-    """Rows p/g/mom/shadow [G, P], c [P], bank [N, P] (a view is fine), slot_client [G]: every
-    operation a separate fp32 rounding, in sgd_scaffold_kernel's order."""
-    lr, wd, mo, gs = (_s32(v) for v in (lr, wd, momentum, grad_scale))
-    d = g * gs + wd * p
-    d = d + (c.reshape(1, -1) - bank[slot_client.long()])
-    if momentum != 0:
-        if first_step:
-            mom.copy_(d)
-        else:
-            mom.copy_(mo * mom + (_s32(1.0) - _s32(dampening)) * d)
-        d = d + mo * mom if nesterov else mom
-    p.copy_(p - lr * d)
-    if shadow is not None:
-        shadow.copy_(p.to(shadow.dtype))
-
-
 def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c):
     """scaffold_finish_kernel's order: the slots from 0 upward, acc from 0; a NaN / Inf delta
     leaves its bank entry untouched and adds nothing."""

@@ -93,31 +93,20 @@ class SGD(_Base):
 
     def step(self, grad_scale: float = 1.0):
         st = self.store
+        # the step, and what it takes between the rows and weight_decay: the operands of its
+        # correction term (none for the plain fused step), then lr
         if self.control is not None:
             c, bank, slot_client = self.control
-            Fn.sgd_scaffold_step(self._rows(st.data), self._rows(st.grad),
-                                 None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
-                                 c, bank, self._rows(slot_client), self.lr, self.weight_decay, self.momentum,
-                                 self.dampening, self.nesterov, first_step=(self.steps == 0),
-                                 grad_scale=grad_scale)
-            st._shadow_version = st.data._version
-            self.steps += 1
-            return
-        if self.prox_mu > 0.0:
+            step, head = Fn.sgd_scaffold_step, (c, bank, self._rows(slot_client), self.lr)
+        elif self.prox_mu > 0.0:
             if self.anchor is None:
                 raise RuntimeError("SGD(prox_mu > 0): call set_anchor() before step()")
-            Fn.sgd_prox_step(self._rows(st.data), self._rows(st.grad),
-                             None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
-                             self.anchor, self.lr, self.prox_mu, self.weight_decay, self.momentum,
-                             self.dampening, self.nesterov, first_step=(self.steps == 0),
-                             grad_scale=grad_scale)
-            st._shadow_version = st.data._version
-            self.steps += 1
-            return
-        Fn.sgd_step(self._rows(st.data), self._rows(st.grad),
-                    None if self.mom is None else self._rows(self.mom), self._shadow_rows(),
-                    self.lr, self.weight_decay, self.momentum, self.dampening, self.nesterov,
-                    first_step=(self.steps == 0), grad_scale=grad_scale)
+            step, head = Fn.sgd_prox_step, (self.anchor, self.lr, self.prox_mu)
+        else:
+            step, head = Fn.sgd_step, (self.lr,)
+        step(self._rows(st.data), self._rows(st.grad), None if self.mom is None else self._rows(self.mom),
+             self._shadow_rows(), *head, self.weight_decay, self.momentum, self.dampening, self.nesterov,
+             first_step=(self.steps == 0), grad_scale=grad_scale)
         st._shadow_version = st.data._version
         self.steps += 1
 

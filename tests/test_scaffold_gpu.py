@@ -351,12 +351,12 @@ def test_kernel_rejects_bad_arguments(cuda):
         args = list(good)
         args[pos] = bad
         assert lib.ddl_scaffold_finish(*args) == 1, pos
-    a = _lib.SGDScaffoldArgs()
-    a.p, a.g, a.c, a.bank, a.slot_client = p, p, p, p, ip
-    a.rows, a.P, a.ld, a.lr = 1, 4, 3, 0.1
-    assert lib.ddl_sgd_scaffold(ctypes.byref(a), s) == 1
+    a = _lib.SGDCorrectedArgs()
+    a.p, a.g, a.ref, a.bank, a.slot_client = p, p, p, p, ip
+    a.rows, a.P, a.ld, a.lr, a.correction = 1, 4, 3, 0.1, _lib.SGD_CONTROL
+    assert lib.ddl_sgd_corrected(ctypes.byref(a), s) == 1
     a.ld, a.slot_client = 4, None
-    assert lib.ddl_sgd_scaffold(ctypes.byref(a), s) == 1
+    assert lib.ddl_sgd_corrected(ctypes.byref(a), s) == 1
 
 
 # ------------------------------------------------------------------------------------- the engine
