@@ -36,6 +36,10 @@ class FLConfig:
     server_beta1: float = 0.9
     server_beta2: float = 0.99
     server_tau: float = 1e-3       # adaptivity floor of fedadagrad / fedadam / fedyogi
+    compress: str | None = None    # compressed uploads: topk | quant (fl/compress.py; None = dense)
+    compress_ratio: float = 0.1    # topk: fraction of the coordinates every client sends
+    compress_bits: int = 4         # quant: bits per coordinate, 2..8
+    error_feedback: bool = True    # keep what the codec dropped per client and add it back next round
     attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider
     malicious: int = 0             # number of malicious clients (ids 0..malicious-1)
     dropout: float = 0.0
@@ -74,6 +78,11 @@ def build_server(cfg: FLConfig, ctx):
         if cfg.server_lr is not None:
             so["lr"] = cfg.server_lr
         kw.update(server_opt=cfg.server_opt, server_opt_kwargs=so)
+    if cfg.compress:
+        if cfg.compress not in ("topk", "quant"):
+            raise ValueError(f"compress must be topk or quant, got {cfg.compress!r}")
+        ck = {"ratio": cfg.compress_ratio} if cfg.compress == "topk" else {"bits": cfg.compress_bits, "seed": cfg.seed}
+        kw.update(compressor=cfg.compress, compressor_kwargs={**ck, "error_feedback": cfg.error_feedback})
     if algo in (FedAvg, Scaffold):
         kw.update(batch_size=cfg.batch_size, local_epochs=cfg.local_epochs)
     return algo(model_fn, DeviceImageDataset(train, ctx.device), parts, **kw)
@@ -89,6 +98,7 @@ def run_fl(cfg: FLConfig, ctx, log=print):
         res = ckpt.run_with_checkpoints(server, cfg.rounds, cfg.checkpoint)
     else:
         res = server.run(cfg.rounds)
+    up = server.uplink_bytes if server.compressor is not None else None
     with JsonlLogger(cfg.jsonl, ctx.rank) as jl:
         for i in range(len(res.test_accuracy)):
             rec = dict(round=i + 1, test_accuracy=res.test_accuracy[i],
@@ -100,6 +110,8 @@ def run_fl(cfg: FLConfig, ctx, log=print):
                 rec["phase_ms"] = res.phase_ms[i]
             if noisy:  # (epsilon, dp_delta)-DP spent after this round (fl/privacy.py, q = K / N)
                 rec["epsilon"] = privacy.epsilon(i + 1, server.K / server.N, cfg.noise_multiplier, cfg.dp_delta)
+            if up is not None and i < len(up):  # bytes the round's reporting clients sent up
+                rec["uplink_bytes"] = up[i]
             jl.log(**rec)
     if log and ctx.rank == 0:
         log(res.as_df(with_throughput=True).to_string(index=False))

@@ -22,6 +22,7 @@ from ..ops import functional as Fn
 from ..runtime import dist as rdist
 from ..utils.metrics import PhaseTimer
 from .aggregate import MeanAggregator, aggregate_into, make_aggregator
+from .compress import make_compressor
 from .local import LocalTrainer
 from .result import RunResult
 from .server_opt import make_server_opt
@@ -42,7 +43,7 @@ class FederatedBase:
                  init_fn=None, eval_every: int = 1, eval_limit: int | None = None, name=None,
                  agg_kwargs=None, dropout: float = 0.0, stragglers: float = 0.0,
                  straggler_slowdown: float = 4.0, deadline: float | None = None, prox_mu: float = 0.0,
-                 server_opt=None, server_opt_kwargs=None):
+                 server_opt=None, server_opt_kwargs=None, compressor=None, compressor_kwargs=None):
         # [NS] heterogeneity: FedProx's proximal term mu/2 |w - w_global|^2 in every client's
         # objective (Li et al. 2020), and a FedOpt server optimizer stepping w_global with the
         # aggregate update as pseudo-gradient (Reddi et al. 2021); both off by default
@@ -51,6 +52,12 @@ class FederatedBase:
         self.prox_mu = float(prox_mu)
         self.server_opt = make_server_opt(server_opt, **(server_opt_kwargs or {})) \
             if isinstance(server_opt, str) else server_opt
+        # [NS] compressed uploads: every reporting client's update goes through a lossy codec with
+        # error feedback (fl/compress.py) before an attack or the server sees it; off by default
+        self.compressor = make_compressor(compressor, **(compressor_kwargs or {})) \
+            if isinstance(compressor, str) else compressor
+        self._uplink: list = []
+        self._slot_tables: dict = {}
         self.ctx = ctx or rdist.context()
         self.dev = self.ctx.device
         self.data = train_data
@@ -73,6 +80,8 @@ class FederatedBase:
         st = self.net.store
         self.w_global = st.data[0].clone()
         self.b_global = st.buffers[0].clone()
+        if self.compressor is not None:
+            self.compressor.bind(self.N, self.w_global.numel(), self.slots, self.dev)
         self.aggregator = aggregator if not isinstance(aggregator, str) else \
             make_aggregator(aggregator, **(agg_kwargs or {}))
         self.mean = MeanAggregator()
@@ -144,6 +153,9 @@ class FederatedBase:
             sd["aggregator"] = self.aggregator.state_dict()
         if self.server_opt is not None:  # the moments m, v: flat rows in this run's parameter layout
             sd["server_opt"] = self.server_opt.state_dict()
+        if self.compressor is not None:  # the error bank (rows in this run's layout), the codec's round
+            sd["compressor"] = self.compressor.state_dict()
+            sd["uplink_bytes"] = self.uplink_bytes
         return sd
 
     def _layout_fix(self, sd: dict):
@@ -178,6 +190,21 @@ class FederatedBase:
             self.aggregator.load_state_dict(sd["aggregator"])
         if self.server_opt is not None and "server_opt" in sd:
             self.server_opt.load_state_dict(sd["server_opt"], like=self.w_global, fix=fix)
+        if self.compressor is not None and "compressor" in sd:
+            self.compressor.load_state_dict(sd["compressor"], fix=fix)
+            self._uplink = [int(b) for b in sd.get("uplink_bytes", [])]
+
+    @property
+    def uplink_bytes(self) -> list[int]:
+        """Bytes the round's reporting clients (of all ranks) sent up, one entry per round, when a
+        compressor is on: the codec's payload for the parameters plus the dense BN buffers. Top-k's
+        counts live on the device until they are read here (as ``ClippedMean.last_norms``)."""
+        for i, v in enumerate(self._uplink):
+            if not isinstance(v, int):
+                nnz, counts, fixed = v
+                n = sum(int(nnz[w, :c].sum()) for w, c in enumerate(counts))
+                self._uplink[i] = self.compressor.uplink_bytes(self.w_global.numel(), n) + fixed
+        return list(self._uplink)
 
     # ------------------------------------------------------------------ helpers
     def _assign(self, chosen):
@@ -274,6 +301,50 @@ class FedAvg(FederatedBase):
 
     def _after_local(self, mine, chosen):
         """The slots hold what the clients trained; no attack has touched the rows yet."""
+        if self.compressor is not None:
+            self._compress(mine, chosen)
+
+    def _slot_table(self, ids):
+        """Device int32 table of the slots' client ids; cached like the coefficients."""
+        key = tuple(ids)
+        t = self._slot_tables.get(key)
+        if t is None:
+            t = torch.tensor(ids, dtype=torch.int32, device=self.dev)
+            if len(self._slot_tables) < 256:
+                self._slot_tables[key] = t
+        return t
+
+    def _compress(self, mine, chosen):
+        """Slot g's row becomes what the server decodes from client mine[g]'s compressed upload; the
+        client's error row takes the residual. BN buffers stay dense. On several ranks the bank is
+        replicated: the round's new rows are all-gathered and written by client id, as Scaffold's."""
+        comp, st, G = self.compressor, self.net.store, len(mine)
+        P, dense = self.w_global.numel(), 4 * self.b_global.numel() * len(chosen)
+        dist_ = self.ctx.is_distributed
+        counts = [len(chosen[w::self.W]) for w in range(self.W)]
+        with self.timer("compress"):
+            nnz = None
+            if G:
+                ids = Fn.check_slot_clients(mine, self.N)  # the table is validated here, where it is built
+                nnz = comp.apply(st.data[:G], self.w_global, self._slot_table(ids))
+            else:
+                comp.skip()  # every rank counts the round: the draws do not depend on the placement
+            if comp.name == "topk":
+                send = torch.zeros(self.slots, dtype=torch.int32, device=self.dev)
+                if G:
+                    send[:G] = nnz
+                self._uplink.append((self.ctx.all_gather_rows(send), counts, dense))
+            else:
+                self._uplink.append(len(chosen) * comp.uplink_bytes(P) + dense)
+            if dist_ and comp.bank is not None:
+                send = torch.zeros(self.slots, P, dtype=torch.float32, device=self.dev)
+                if G:
+                    send[:G] = comp.bank[torch.as_tensor(mine, dtype=torch.int64, device=self.dev)]
+                got = self.ctx.all_gather_rows(send)  # [W, slots, P]
+                for w in range(self.W):
+                    theirs = [int(c) for c in chosen[w::self.W]]
+                    if theirs and w != self.ctx.rank:
+                        comp.bank[torch.as_tensor(theirs, dtype=torch.int64, device=self.dev)] = got[w, :len(theirs)]
 
     def _coeffs(self, mine, total):
         """Device tensor of the n_k / n weights of my clients; cached per (clients, total), since
@@ -293,6 +364,8 @@ class FedAvg(FederatedBase):
         chosen = self._sample()
         if len(chosen) == 0:  # every sampled client dropped out: the server model stays
             self.round_idx += 1
+            if self.compressor is not None:
+                self._uplink.append(0)
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
         mine, counts = self._assign(chosen)
         G = len(mine)
@@ -391,6 +464,9 @@ class Scaffold(FedAvg):
         super().__init__(*a, **kw)
         if self.prox_mu > 0.0:
             raise ValueError("Scaffold: the control variates and prox_mu > 0 are not combined")
+        if self.compressor is not None:
+            raise ValueError("Scaffold: the control variates are formed from the uncompressed rows; "
+                             "a compressor is not combined with them")
         P = self.w_global.numel()
         self.c_global = torch.zeros(P, dtype=torch.float32, device=self.dev)
         self.c_bank = torch.zeros(self.N, P, dtype=torch.float32, device=self.dev)
@@ -488,6 +564,8 @@ class FedSGD(FederatedBase):
             raise ValueError("FedSGD: the proximal term vanishes at w_global, prox_mu has no effect")
         if self.server_opt is not None:
             raise ValueError("FedSGD: a server optimizer on gradients is not supported (use FedAvg)")
+        if self.compressor is not None:
+            raise ValueError("FedSGD: the compressor works on trained rows (use FedAvg or FedSgdWeight)")
         self.max_mb = max_microbatch
         self.g_global = torch.zeros_like(self.w_global)
 

@@ -192,6 +192,11 @@ _SIGS = {
     "ddl_server_opt_rows": [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     # scaffold.hip
     "ddl_scaffold_finish": [vp, i64, vp, vp, vp, i64, vp, vp, i32, f32, vp, i64, i32, vp],
+    # compress.hip
+    "ddl_compress_row_blocks": [i32, i64],
+    "ddl_topk_workspace": [i32],
+    "ddl_topk_compress": [vp, i64, vp, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp],
+    "ddl_quantize_compress": [vp, i64, vp, vp, i64, vp, i32, i64, i32, u64, u32, vp, vp, vp],
 }
 
 # fp32-activation twins of the templated memory-bound launchers (nn_ops.hip): same signatures
@@ -236,7 +241,8 @@ _SIGS.update({
 })
 _RESTYPES = {"ddl_convf32_slots": ctypes.c_longlong, "ddl_convf32_workspace": ctypes.c_longlong,
              "ddl_x6h_workspace": ctypes.c_longlong, "ddl_x6h_slots": ctypes.c_longlong, "ddl_bnf_fold_ws": ctypes.c_longlong, "ddl_bnf_fold_tickets": ctypes.c_longlong,
-             "ddl_gram_f32_workspace": ctypes.c_longlong, "ddl_update_sqnorm_workspace": ctypes.c_longlong}
+             "ddl_gram_f32_workspace": ctypes.c_longlong, "ddl_update_sqnorm_workspace": ctypes.c_longlong,
+             "ddl_topk_workspace": ctypes.c_longlong}
 
 _OPTIONAL_SIGS: dict[str, list] = {}
 

@@ -1324,6 +1324,87 @@ def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c=F
     return dc
 
 
+# ------------------------------------------------------------- compressed uploads (compress.hip)
+def _compress_check(name, rows, x, bank, slot_client):
+    G, P = rows.shape
+    assert rows.dtype == torch.float32 and G >= 1
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == P and x.device == rows.device
+    if slot_client is not None:
+        assert slot_client.dtype == torch.int32 and slot_client.dim() == 1 and slot_client.numel() == G
+        assert slot_client.device == rows.device
+    if bank is not None:
+        assert slot_client is not None, f"{name}: a bank needs the slot table"
+        assert bank.dtype == torch.float32 and bank.dim() == 2 and bank.shape[1] == P and bank.device == rows.device
+        assert bank.shape[0] == 1 or bank.stride(0) >= P
+        if not slot_client.is_cuda:  # a host table is checked here; a device table where it was built
+            check_slot_clients(slot_client.tolist(), bank.shape[0])
+    if rows.is_cuda:
+        assert rows.stride(1) == 1 and (bank is None or bank.stride(1) == 1), f"{name}: unit inner strides are needed"
+        assert slot_client is None or slot_client.is_contiguous()
+    # a single row's stride is never used: a multiple of 4 keeps the 16-B path open for any P
+    ldy = rows.stride(0) if G > 1 else (P + 3) // 4 * 4
+    ld = (P + 3) // 4 * 4 if bank is None or bank.shape[0] <= 1 else bank.stride(0)
+    return G, P, ldy, ld
+
+
+def topk_compress(rows, x, bank, slot_client, k: int, nnz):
+    """Top-k sparsification with error feedback, in place (compress.hip): with u = (rows[g] - x) +
+    bank[slot_client[g]] (no bank: u = rows[g] - x), the entries whose magnitude reaches tau_g, the
+    k-th largest finite non-zero magnitude of the row (bit patterns compared; all ties kept; the
+    smallest when the row has fewer than k), become x + u in rows[g] and +0 in the bank row, the
+    others the bits of x and u. A NaN / Inf u is passed through as x + u and leaves its bank entry.
+    nnz [G] int32 on the rows' device receives the number of kept entries, without a host
+    synchronisation. An exact radix select: 10 P floats moved per row."""
+    G, P, ldy, ld = _compress_check("topk_compress", rows, x, bank, slot_client)
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"topk_compress: k must be >= 1, got {k}")
+    assert nnz.dtype == torch.int32 and nnz.numel() == G and nnz.is_contiguous() and nnz.device == rows.device
+    if P == 0:
+        nnz.zero_()
+        return nnz
+    if not rows.is_cuda:
+        ref.topk_compress(rows, x, bank, slot_client, k, nnz)
+        return nnz
+    lib = _lib.kernels()
+    cap = lib.ddl_topk_workspace(G)
+    work = torch.empty(cap, dtype=torch.int32, device=rows.device)
+    check(lib.ddl_topk_compress(ptr(rows), ldy, ptr(x), ptr(bank), ld, ptr(slot_client), G, P, k, ptr(nnz),
+                                ptr(work), cap, stream()), "topk_compress")
+    nnz._keep = work  # the scratch must outlive the (asynchronous) launches
+    return nnz
+
+
+def quantize_compress(rows, x, bank, slot_client, bits: int, seed: int, round: int, levels=None, scales=None):
+    """QSGD-style stochastic quantization with error feedback, in place (compress.hip): per bucket of
+    256 columns the scale s is the largest finite |u|, L = 2^(bits-1) - 1, a = (|u| / s) * L,
+    level = min(L, floor(a) + (frac(a) >= r)) with r in (0, 1] from Philox keyed by ``seed`` at
+    counter (column >> 2, client, tag, round); q = sign(u) * s * (level / L); rows[g] = x + q and the
+    bank row takes u - q. slot_client names the clients (it keys the draws) also without a bank.
+    levels (int8 [G, P]) and scales (fp32 [G, ceil(P / 256)]), when given, receive what a wire would
+    carry. One pass, 5 P floats per row."""
+    G, P, ldy, ld = _compress_check("quantize_compress", rows, x, bank, slot_client)
+    bits = int(bits)
+    if not 2 <= bits <= 8:
+        raise ValueError(f"quantize_compress: bits must lie in 2..8, got {bits}")
+    assert slot_client is not None, "quantize_compress: the slot table keys the draws"
+    nb = (P + 255) // 256
+    if levels is not None:
+        assert levels.dtype == torch.int8 and levels.shape == (G, P) and levels.is_contiguous()
+        assert levels.device == rows.device
+    if scales is not None:
+        assert scales.dtype == torch.float32 and scales.shape == (G, nb) and scales.is_contiguous()
+        assert scales.device == rows.device
+    if P == 0:
+        return
+    if not rows.is_cuda:
+        ref.quantize_compress(rows, x, bank, slot_client, bits, int(seed), int(round), levels, scales)
+        return
+    check(_lib.kernels().ddl_quantize_compress(ptr(rows), ldy, ptr(x), ptr(bank), ld, ptr(slot_client), G, P, bits,
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF, ptr(levels),
+                                               ptr(scales), stream()), "quantize_compress")
+
+
 SERVER_OPT_KINDS = ref.SERVER_OPT_KINDS  # sgdm (FedAvgM), adagrad, adam, yogi
 
 

@@ -526,6 +526,80 @@ def apply_update(out, center, delta, std=0.0, seed=0, round=0, offset=0):
     out.copy_(o)
 
 
+# ------------------------------------------- compressed uploads (compress.hip), fp32 torch twins
+QUANT_TAG = 0x510E527F
+_EXP_MASK = 0x7F800000
+
+
+def _corrected_update(rows, x, bank, ids, g):
+    """-> (u, e, magnitude bits, finite): u = (y - x) + e, or y - x without a bank."""
+    e = None if bank is None else bank[ids[g]]
+    d = rows[g] - x
+    u = (d if e is None else d + e).contiguous()
+    key = u.view(torch.int32) & 0x7FFFFFFF
+    return u, e, key, key < _EXP_MASK
+
+
+def topk_compress(rows, x, bank, slot_client, k, nnz):
+    """compress.hip's top-k, bit for bit: tau is the k-th largest magnitude bit pattern among the
+    finite non-zero ones (the smallest when there are fewer), every entry that reaches it is kept."""
+    ids = None if slot_client is None else slot_client.tolist()
+    for g in range(rows.shape[0]):
+        u, e, key, finite = _corrected_update(rows, x, bank, ids, g)
+        counts = finite & (key != 0)
+        n = int(counts.sum())
+        keep = torch.zeros_like(counts)
+        if n:
+            tau = torch.sort(key[counts], descending=True).values[min(int(k), n) - 1]
+            keep = counts & (key >= tau)
+        rows[g].copy_(torch.where(keep | ~finite, x + u, x))
+        if e is not None:
+            e.copy_(torch.where(finite, torch.where(keep, torch.zeros_like(u), u), e))
+        nnz[g] = int(keep.sum())
+
+
+def quantize_draws(P: int, client: int, seed: int, round: int):
+    """r [P] in (0, 1]: word j & 3 of philox4x32(counter (j >> 2, client, QUANT_TAG, round), key seed)."""
+    q = torch.arange((P + 3) >> 2, dtype=torch.int64)
+    zero = torch.zeros_like(q)
+    r = philox4x32_t(q & _M32, zero + (int(client) & _M32), zero + QUANT_TAG, zero + (round & _M32),
+                     seed & _M32, (seed >> 32) & _M32)
+    w = torch.stack(r, 1).reshape(-1)[:P]
+    return ((w >> 8).float() + 1.0) * (1.0 / 16777216.0)
+
+
+def quantize_compress(rows, x, bank, slot_client, bits, seed, round, levels=None, scales=None):
+    """quantize_kernel's operations in its order, in fp32 torch."""
+    G, P = rows.shape
+    L = (1 << (bits - 1)) - 1
+    fL = _s32(float(L))
+    nb = (P + 255) // 256
+    ids = slot_client.tolist()
+    for g in range(G):
+        u, e, key, finite = _corrected_update(rows, x, bank, ids, g)
+        mag = torch.where(finite, key, torch.zeros_like(key)).view(torch.float32)
+        pad = torch.zeros(nb * 256)
+        pad[:P] = mag
+        s = pad.reshape(nb, 256).max(1).values
+        sj = s.repeat_interleave(256)[:P]
+        live = finite & (sj > 0)
+        a = (mag / torch.where(live, sj, torch.ones_like(sj))) * fL
+        fl = torch.floor(a)
+        up = (a - fl) >= quantize_draws(P, ids[g], seed, round)
+        lv = torch.clamp(fl + up.float(), max=float(L))
+        lv = torch.where(live, lv, torch.zeros_like(lv))
+        q = sj * (lv / fL)
+        neg = u.view(torch.int32) < 0
+        q = torch.where(neg, -q, q)
+        rows[g].copy_(torch.where(finite, x + q, x + u))
+        if e is not None:
+            e.copy_(torch.where(finite, u - q, e))
+        if levels is not None:
+            levels[g].copy_(torch.where(neg, -lv, lv).to(torch.int8))
+        if scales is not None:
+            scales[g].copy_(s)
+
+
 def mse_kl(xr, x, mu, lv, kl_w=1.0):
     mse = ((xr - x) ** 2).sum()
     kl = -0.5 * (1 + lv - mu * mu - lv.exp()).sum()
