@@ -45,6 +45,37 @@ template <int W> __device__ __forceinline__ void stv(float* p, const fvec<W>& x)
   else *p = x.v[0];
 }
 
+// W 32-bit words in registers: the integer rows of secagg.hip (sums mod 2^32)
+template <int W> struct uvec {
+  uint32_t v[W];
+  __device__ __forceinline__ uint32_t& operator[](int i) { return v[i]; }
+  __device__ __forceinline__ const uint32_t& operator[](int i) const { return v[i]; }
+};
+
+template <int W> __device__ __forceinline__ uvec<W> uzero() {
+  uvec<W> r;
+#pragma unroll
+  for (int i = 0; i < W; ++i) r.v[i] = 0u;
+  return r;
+}
+
+template <int W> __device__ __forceinline__ uvec<W> ldv(const uint32_t* p) {
+  static_assert(W == 1 || W == 4, "one element or one 16-byte quad");
+  uvec<W> r;
+  if constexpr (W == 4) {
+    const uint4 t = *(const uint4*)p;
+    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+  } else {
+    r.v[0] = *p;
+  }
+  return r;
+}
+
+template <int W> __device__ __forceinline__ void stv(uint32_t* p, const uvec<W>& x) {
+  if constexpr (W == 4) *(uint4*)p = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+  else *p = x.v[0];
+}
+
 // the bf16 image of x (W = 4: one 8-byte store)
 template <int W> __device__ __forceinline__ void stv_bf16(bf16_t* p, const fvec<W>& x) {
   if constexpr (W == 4) {

@@ -23,13 +23,15 @@ class FLConfig:
     rounds: int = 10
     iid: bool = True
     seed: int = 10
-    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped
+    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped | secagg
     trim: float = 0.1
     krum_f: int = 1
-    clip_norm: float = 1.0         # clipped: L2 bound C on every client update
+    clip_norm: float | None = None  # clipped / secagg: L2 bound C on every client update (default: 1.0 / none)
     noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
     agg_weighting: str = "samples"  # clipped: samples (n_k / n) | uniform (1 / K)
     dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
+    secagg_bits: int = 20          # secagg: fractional bits of the fixed-point uploads, 8..30
+    secagg_min_survivors: int = 2  # secagg: a round with fewer reporting clients is aborted
     prox_mu: float = 0.0           # FedProx: mu of the proximal term mu/2 |w - w_global|^2 (0 = off)
     server_opt: str | None = None  # FedOpt server optimizer: fedavgm | fedadagrad | fedadam | fedyogi
     server_lr: float | None = None  # its step size (default 1.0 for fedavgm, 0.01 for the adaptive ones)
@@ -66,9 +68,13 @@ def build_server(cfg: FLConfig, ctx):
     attack = make_attack(cfg.attack, list(range(cfg.malicious))) if cfg.attack else None
     algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight,
             "scaffold": Scaffold}[cfg.algorithm]
+    secure = cfg.aggregator.lower() in ("secagg", "secure", "secure_mean")
+    # without --clip-norm: the clipped mean bounds at 1.0, secure aggregation does not clip
+    clip = cfg.clip_norm if cfg.clip_norm is not None else (float("inf") if secure else 1.0)
     kw = dict(lr=cfg.lr, client_fraction=cfg.client_fraction, seed=cfg.seed,
               test_data=DeviceImageDataset(test, ctx.device), aggregator=cfg.aggregator,
-              agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": cfg.clip_norm,
+              agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": clip, "frac_bits": cfg.secagg_bits,
+                          "min_survivors": cfg.secagg_min_survivors,
                           "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
                           "weighting": cfg.agg_weighting}, attack=attack, ctx=ctx,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
@@ -99,6 +105,7 @@ def run_fl(cfg: FLConfig, ctx, log=print):
     else:
         res = server.run(cfg.rounds)
     up = server.uplink_bytes if server.compressor is not None else None
+    secure = getattr(server.aggregator, "name", None) == "secagg"
     with JsonlLogger(cfg.jsonl, ctx.rank) as jl:
         for i in range(len(res.test_accuracy)):
             rec = dict(round=i + 1, test_accuracy=res.test_accuracy[i],
@@ -112,6 +119,10 @@ def run_fl(cfg: FLConfig, ctx, log=print):
                 rec["epsilon"] = privacy.epsilon(i + 1, server.K / server.N, cfg.noise_multiplier, cfg.dp_delta)
             if up is not None and i < len(up):  # bytes the round's reporting clients sent up
                 rec["uplink_bytes"] = up[i]
+            if secure:  # host-known: the sampled clients, those that reported, whether the server opened
+                gone = sum(len(lst[i]) for lst in (server.dropped, server.straggled) if i < len(lst))
+                rec.update(secagg_cohort=server.K, secagg_survivors=server.K - gone,
+                           secagg_aborted=i in server.aggregator.aborted)
             jl.log(**rec)
     if log and ctx.rank == 0:
         log(res.as_df(with_throughput=True).to_string(index=False))

@@ -20,6 +20,10 @@
 * ``ClippedMean`` — norm bounding (Sun et al. 2019) and DP-FedAvg (McMahan et al. 2018)
   [north-star]: each update clipped to L2 norm C, then the weighted mean, optionally plus Gaussian
   noise; streaming kernels (clip_agg.hip), the mean's cross-rank route, any number of clients.
+* ``SecureMean`` — secure aggregation (Bonawitz et al. 2017) [north-star]: the clipped mean on
+  fixed-point uploads under pairwise masks that cancel in the sum, with recovery from dropped clients
+  (secagg.hip). Key agreement and secret sharing are simulated: every mask is a pure function of
+  (seed, round, pair, coordinate).
 Robust rules operate on client *updates* (w_k - w_global) — distances between raw weights would
 cancel catastrophically in fp32.
 """
@@ -173,6 +177,151 @@ class ClippedMean(MeanAggregator):
         self.rounds, self.last_k = int(sd["rounds"]), int(sd.get("last_k", 0))
 
 
+class SecureMean(ClippedMean):
+    """Secure aggregation (Bonawitz et al., CCS 2017) [north-star]: the clipped weighted mean, but
+    the server only ever sees each client's update as fixed-point words under pairwise one-time
+    masks that cancel in the sum (plus a self mask per client), and opens nothing but the sum.
+
+    Per GPU: update_sqnorm -> clip_scales (a non-finite row gets weight 0) -> secagg_mask into a
+    cached ``uploads [slots, P]`` int32 buffer: client i uploads rint(cs_i u_i 2^f) + masks mod 2^32,
+    the masks taken against the round's *cohort* (everyone sampled, before dropout and deadline).
+    One rank opens the uploads directly; several ranks sum theirs (secagg_sum), all-gather the int32
+    partials and open the [W, P] stack on every rank. Opening removes the survivors' self masks and
+    the pair masks the dropped clients left behind. The sums are integers mod 2^32, so the result
+    has the same bits on any placement of the clients over ranks. apply_update then adds the centre
+    and the (central) DP noise as in ``ClippedMean``.
+
+    Key agreement and secret sharing are simulated: every mask is a pure function of (seed, round,
+    pair, coordinate), so what is modelled is the arithmetic and its cost, not the cryptography.
+    A round with fewer than ``min_survivors`` reporting clients is aborted: nothing is opened (a
+    lone upload would be that client's plaintext), ``out`` becomes the centre (zero without one), the
+    round counter still advances. The engine announces each round with ``begin_round``. Only the
+    parameters are protected: the engine's BN buffers keep the plain mean."""
+    name = "secagg"
+
+    def __init__(self, frac_bits: int = 20, clip: float = math.inf, min_survivors: int = 2,
+                 noise_multiplier: float = 0.0, seed: int = 0, weighting: str = "samples",
+                 ordered: bool | None = None):
+        super().__init__(clip, noise_multiplier, seed, weighting, ordered)
+        self.frac_bits = int(frac_bits)
+        if not Fn.SECAGG_BITS[0] <= self.frac_bits <= Fn.SECAGG_BITS[1]:
+            raise ValueError(f"frac_bits must lie in {Fn.SECAGG_BITS[0]}..{Fn.SECAGG_BITS[1]}, got {frac_bits}")
+        self.min_survivors = int(min_survivors)
+        if self.min_survivors < 1:
+            raise ValueError(f"min_survivors must be >= 1, got {min_survivors}")
+        if self.noise_multiplier > 0.0 and not math.isfinite(self.clip):
+            raise ValueError("noise_multiplier > 0 needs a finite clip: the noise is scaled by it")
+        self.aborted: list[int] = []
+        self._round = None     # (cohort, survivors, dropped, this rank's clients) of the announced round
+        self._uploads: dict = {}
+        self._tables: dict = {}
+        self._last = None
+        self._sat = None
+
+    def begin_round(self, cohort, survivors, clients) -> None:
+        """The round's cohort (every sampled client), the survivors (those that report, on all
+        ranks) and this rank's clients in slot order; host lists, the same on every rank but for
+        the last."""
+        cohort, survivors = Fn.secagg_ids(cohort, "cohort"), Fn.secagg_ids(survivors, "survivors")
+        clients = Fn.secagg_ids(clients, "clients")
+        if not set(survivors) <= set(cohort) or not set(clients) <= set(survivors):
+            raise ValueError("secagg: clients must be survivors and survivors members of the cohort")
+        alive = set(survivors)
+        self._round = (cohort, survivors, [c for c in cohort if c not in alive], clients)
+
+    def _table(self, ids, dev):
+        key = (tuple(ids), dev)
+        t = self._tables.get(key)
+        if t is None:
+            t = torch.tensor(ids, dtype=torch.int32, device=dev)
+            if len(self._tables) < 256:
+                self._tables[key] = t
+        return t
+
+    def abort_round(self, out: torch.Tensor | None = None, center: torch.Tensor | None = None):
+        """Too few survivors: nothing is opened, the model stays, the round is counted."""
+        if out is not None:
+            if center is None:
+                out.zero_()
+            elif out is not center:
+                out.copy_(center)
+        self.aborted.append(self.rounds)
+        self.rounds += 1
+        self._round = self._last = self._sat = self._norms = None
+
+    def __call__(self, ctx, rows: torch.Tensor, coeffs: torch.Tensor, out: torch.Tensor,
+                 center: torch.Tensor | None = None, counts: list[int] | None = None):
+        if self._round is None:
+            raise RuntimeError("secagg: begin_round(cohort, survivors, clients) must announce the round")
+        cohort, survivors, dropped, clients = self._round
+        G, P = rows.shape
+        if len(clients) != G:
+            raise ValueError(f"secagg: {G} rows for the {len(clients)} clients announced")
+        K_r = len(survivors)
+        if counts is not None and int(sum(counts)) != K_r:
+            raise ValueError(f"secagg: {int(sum(counts))} rows over the ranks for {K_r} survivors")
+        if K_r < self.min_survivors:
+            self.last_k = K_r
+            self.abort_round(out, center)
+            return out
+        dev = out.device
+        delta = self._delta.get((P, dev))
+        if delta is None:
+            delta = self._delta[(P, dev)] = torch.empty(P, dtype=torch.float32, device=dev)
+        slots = max(G, 1)
+        up = self._uploads.get((P, dev))
+        if up is None or up.shape[0] < slots:
+            up = self._uploads[(P, dev)] = torch.empty(slots, P, dtype=torch.int32, device=dev)
+        if G == 0:
+            self._norms = self._last = self._sat = None
+        else:
+            if rows.stride(1) != 1:
+                rows = rows.contiguous()
+            if self.weighting == "uniform":
+                coeffs = self._uniform.get((G, K_r, dev))
+                if coeffs is None:
+                    coeffs = self._uniform[(G, K_r, dev)] = torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev)
+            sq = Fn.update_sqnorm(rows, center)
+            self._norms, cs = Fn.clip_scales(sq, coeffs, self.clip)
+            self._sat = torch.empty(G, dtype=torch.int32, device=dev)
+            self._last = Fn.secagg_mask(rows, center, cs, self._table(clients, dev), self._table(cohort, dev),
+                                        self.frac_bits, self.seed, self.rounds, up[:G], self._sat)
+        alive = self._table(survivors, dev)
+        gone = self._table(dropped, dev) if dropped else None
+        if not ctx.is_distributed:
+            Fn.secagg_open(up[:G], alive, gone, self.frac_bits, self.seed, self.rounds, delta)
+        else:
+            part = torch.zeros(P, dtype=torch.int32, device=dev)
+            if G:
+                Fn.secagg_sum(up[:G], part)
+            Fn.secagg_open(ctx.all_gather_rows(part), alive, gone, self.frac_bits, self.seed, self.rounds, delta)
+        std = self.noise_multiplier * self.clip / K_r if self.noise_multiplier > 0.0 else 0.0
+        Fn.apply_update(out, center, delta, std, self.seed, self.rounds)
+        self.rounds += 1
+        self.last_k = K_r
+        self._round = None
+        return out
+
+    @property
+    def last_uploads(self):
+        """What the server saw of this rank's clients in the last round: int32 [G, P] masked words
+        (None for an aborted round or a rank without clients)."""
+        return self._last
+
+    @property
+    def last_saturated(self) -> list[int]:
+        """Per client of this rank, the coordinates that hit the fixed-point range or were NaN in
+        the last round (syncs the device)."""
+        return [] if self._sat is None else self._sat.tolist()
+
+    def state_dict(self) -> dict:
+        return {"rounds": self.rounds, "last_k": self.last_k, "aborted": list(self.aborted)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        super().load_state_dict(sd)
+        self.aborted = [int(r) for r in sd.get("aborted", [])]
+
+
 class _Sharded:
     """Helpers to move [G_i, P] client rows into coordinate shards [K, P/W] on every rank."""
     needs_all = True
@@ -318,4 +467,7 @@ def make_aggregator(name: str, **kw):
     if name in ("clipped", "clipped_mean", "norm_clip"):
         return ClippedMean(kw.get("clip", 1.0), kw.get("noise_multiplier", 0.0), kw.get("seed", 0),
                            kw.get("weighting", "samples"))
+    if name in ("secagg", "secure", "secure_mean"):
+        return SecureMean(kw.get("frac_bits", 20), kw.get("clip", math.inf), kw.get("min_survivors", 2),
+                          kw.get("noise_multiplier", 0.0), kw.get("seed", 0), kw.get("weighting", "samples"))
     raise ValueError(f"unknown aggregator {name}")

@@ -117,6 +117,9 @@ class FederatedBase:
 
     def _sample(self):
         chosen = self.rng.choice(self.N, self.K, replace=False)
+        # the round's cohort: everyone sampled, before the dropout and deadline filters (secure
+        # aggregation masks against it; the clients that never report are what it recovers from)
+        self.cohort = [int(c) for c in chosen]
         if self.dropout > 0:
             alive = self.fail_rng.random(len(chosen)) >= self.dropout
             self.dropped.append([int(c) for c in chosen[~alive]])
@@ -217,6 +220,19 @@ class FederatedBase:
         assignment above): the robust rules break exact ties by it, so a run gives the same
         aggregate on one GPU and on W."""
         return [l * self.W + w for w in range(self.W) for l in range(counts[w])]
+
+    def _announce(self, chosen, mine) -> bool:
+        """Tell an aggregator that wants it (``SecureMean.begin_round``) the round's cohort, its
+        survivors and this rank's clients. No survivor at all: the aggregator counts an aborted
+        round, as the engine skips the aggregation. BN buffers keep the plain mean either way.
+        -> whether the aggregator was told."""
+        agg = self.aggregator
+        if not hasattr(agg, "begin_round"):
+            return False
+        agg.begin_round(self.cohort, [int(c) for c in chosen], mine)
+        if len(chosen) == 0:
+            agg.abort_round()
+        return True
 
     def _download(self, G):
         st = self.net.store
@@ -364,10 +380,12 @@ class FedAvg(FederatedBase):
         chosen = self._sample()
         if len(chosen) == 0:  # every sampled client dropped out: the server model stays
             self.round_idx += 1
+            self._announce(chosen, [])
             if self.compressor is not None:
                 self._uplink.append(0)
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
         mine, counts = self._assign(chosen)
+        self._announce(chosen, mine)
         G = len(mine)
         total = float(sum(self.counts[int(c)] for c in chosen))
         r = self.round_idx
@@ -467,6 +485,9 @@ class Scaffold(FedAvg):
         if self.compressor is not None:
             raise ValueError("Scaffold: the control variates are formed from the uncompressed rows; "
                              "a compressor is not combined with them")
+        if getattr(self.aggregator, "name", None) == "secagg":
+            raise ValueError("Scaffold: the control-variate sums would stay in the clear; secure "
+                             "aggregation is not combined with them")
         P = self.w_global.numel()
         self.c_global = torch.zeros(P, dtype=torch.float32, device=self.dev)
         self.c_bank = torch.zeros(self.N, P, dtype=torch.float32, device=self.dev)
@@ -575,8 +596,10 @@ class FedSGD(FederatedBase):
         chosen = self._sample()
         if len(chosen) == 0:
             self.round_idx += 1
+            self._announce(chosen, [])
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
         mine, counts = self._assign(chosen)
+        self._announce(chosen, mine)
         G = len(mine)
         total = float(sum(self.counts[int(c)] for c in chosen))
         self._download(G)

@@ -197,6 +197,11 @@ _SIGS = {
     "ddl_topk_workspace": [i32],
     "ddl_topk_compress": [vp, i64, vp, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp],
     "ddl_quantize_compress": [vp, i64, vp, vp, i64, vp, i32, i64, i32, u64, u32, vp, vp, vp],
+    # secagg.hip
+    "ddl_secagg_row_blocks": [i32, i64],
+    "ddl_secagg_mask": [vp, i64, vp, vp, vp, i32, i64, vp, i32, i32, u64, u32, vp, i64, vp, i32, vp],
+    "ddl_secagg_sum": [vp, i64, i32, i64, vp, vp],
+    "ddl_secagg_open": [vp, i64, i32, i64, vp, i32, vp, i32, i32, u64, u32, vp, vp],
 }
 
 # fp32-activation twins of the templated memory-bound launchers (nn_ops.hip): same signatures

@@ -1405,6 +1405,141 @@ def quantize_compress(rows, x, bank, slot_client, bits: int, seed: int, round: i
                                                ptr(scales), stream()), "quantize_compress")
 
 
+# ------------------------------------------------------------- secure aggregation (secagg.hip)
+SECAGG_MAX_CLIENTS = ref.SECAGG_MAX_CLIENTS
+SECAGG_BITS = (8, 30)
+
+
+def secagg_ids(ids, what: str = "clients"):
+    """The host-side check of a secure-aggregation id list before it goes to the device: every id
+    in [0, 65536) (a pair of them packs into one Philox counter word) and all distinct. The kernels
+    take the tables as they are. -> the ids as a list of ints."""
+    ids = [int(i) for i in ids]
+    if any(i < 0 or i >= SECAGG_MAX_CLIENTS for i in ids):
+        raise ValueError(f"secagg: {what} must lie in [0, {SECAGG_MAX_CLIENTS}), got {ids}")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"secagg: {what} names one client twice, got {ids}")
+    return ids
+
+
+def _secagg_bits(name, frac_bits):
+    frac_bits = int(frac_bits)
+    if not SECAGG_BITS[0] <= frac_bits <= SECAGG_BITS[1]:
+        raise ValueError(f"{name}: frac_bits must lie in {SECAGG_BITS[0]}..{SECAGG_BITS[1]}, got {frac_bits}")
+    return frac_bits
+
+
+def _secagg_table(name, t, dev, what, allow_empty=False):
+    """An id table: int32, 1-D, contiguous, on ``dev``; a host table's contents are checked here."""
+    assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == dev, f"{name}: {what}"
+    if t.numel() == 0 and not allow_empty:
+        raise ValueError(f"{name}: {what} is empty")
+    if t.numel() > SECAGG_MAX_CLIENTS:
+        raise ValueError(f"{name}: {what} holds more than {SECAGG_MAX_CLIENTS} clients")
+    if not t.is_cuda:
+        secagg_ids(t.tolist(), what)
+    return t.numel()
+
+
+def _secagg_words(name, words, dev):
+    assert words.dtype == torch.int32 and words.dim() == 2 and words.device == dev, f"{name}: words"
+    R, P = words.shape
+    assert R >= 1 and (P == 0 or words.stride(1) == 1) and (R == 1 or words.stride(0) >= P), f"{name}: words"
+    # a single row's stride is never used: a multiple of 4 keeps the 16-B path open for any P
+    return R, P, words.stride(0) if R > 1 else (P + 3) // 4 * 4
+
+
+# the mask kernel's form for 2..8 local rows: a thread holds its quad of every row and a pair of two
+# local clients costs one Philox call instead of two (the same integer sums regrouped: the same bits)
+SECAGG_PAIR_SHARED = True
+
+
+def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits: int, seed: int, round: int, words, sat,
+                pair_shared: bool | None = None):
+    """The masked fixed-point uploads of the slots' clients (secagg.hip): slot g holds client
+    i = slot_client[g] of the round's ``cohort`` (n ids, int32, everyone sampled, i among them), and
+
+        q = clamp(rint(fl32(cs[g] * fl32(rows[g] - center)) * 2^frac_bits), +-lim),  lim = (2^31 - 1) // n
+        words[g] = q + m(i, i) + sum_{j in cohort, j != i} s_ij m(min(i, j), max(i, j))   mod 2^32
+
+    with m a Philox word keyed by (seed, round, pair, coordinate) and s_ij = +1 for i < j, -1 for
+    i > j. sat [G] int32 counts the coordinates of each row that hit +-lim or were NaN (q = 0). A row
+    with cs[g] == 0 is not read: its words are the bare masks. center None: the rows are the updates.
+    ``pair_shared`` picks the kernel's form (None: ``SECAGG_PAIR_SHARED``); both give the same bits.
+    Nothing is copied to the host. -> words."""
+    G, P = rows.shape
+    dev = rows.device
+    frac_bits = _secagg_bits("secagg_mask", frac_bits)
+    assert rows.dtype == torch.float32 and G >= 1 and (P == 0 or rows.stride(1) == 1)
+    assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == P
+                              and center.device == dev)
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == G and cs.device == dev
+    n = _secagg_table("secagg_mask", cohort, dev, "cohort")
+    assert _secagg_table("secagg_mask", slot_client, dev, "slot_client") == G
+    if not cohort.is_cuda and not set(slot_client.tolist()) <= set(cohort.tolist()):
+        raise ValueError("secagg_mask: a slot's client is not in the cohort")
+    R, Pw, ldw = _secagg_words("secagg_mask", words, dev)
+    assert (R, Pw) == (G, P), "secagg_mask: words must be [G, P]"
+    assert sat.dtype == torch.int32 and sat.numel() == G and sat.is_contiguous() and sat.device == dev
+    if P == 0:
+        sat.zero_()
+        return words
+    seed, round = int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF
+    if not rows.is_cuda:
+        ref.secagg_mask(rows, center, cs, slot_client, cohort, frac_bits, seed, round, words, sat)
+        return words
+    ld = rows.stride(0) if G > 1 else (P + 3) // 4 * 4
+    assert ld >= P
+    check(_lib.kernels().ddl_secagg_mask(ptr(rows), ld, ptr(center), ptr(cs), ptr(slot_client), G, P, ptr(cohort), n,
+                                         frac_bits, seed, round, ptr(words), ldw, ptr(sat),
+                                         int(SECAGG_PAIR_SHARED if pair_shared is None else bool(pair_shared)),
+                                         stream()), "secagg_mask")
+    return words
+
+
+def secagg_sum(words, out):
+    """out [P] int32 = the sum mod 2^32 of the rows of words [R, P] int32 (secagg.hip): a rank's
+    partial of the masked uploads it holds."""
+    R, P, ldw = _secagg_words("secagg_sum", words, out.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == P
+    if P == 0:
+        return out
+    if not words.is_cuda:
+        ref.secagg_sum(words, out)
+        return out
+    check(_lib.kernels().ddl_secagg_sum(ptr(words), ldw, R, P, ptr(out), stream()), "secagg_sum")
+    return out
+
+
+def secagg_open(words, survivors, dropped, frac_bits: int, seed: int, round: int, delta):
+    """delta [P] fp32 = the aggregate the masked rows hide (secagg.hip): the rows of words [R, P]
+    (uploads, or per-rank partials of them) are summed mod 2^32, the self masks of the ``survivors``
+    and the pair masks they share with the ``dropped`` clients (int32 id tables; dropped may be None)
+    are taken off, and the remaining int32 is scaled by 2^-frac_bits. survivors + dropped must be
+    the cohort the uploads were masked against, or the result is noise. -> delta."""
+    dev = delta.device
+    frac_bits = _secagg_bits("secagg_open", frac_bits)
+    R, P, ldw = _secagg_words("secagg_open", words, dev)
+    assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == P
+    ns = _secagg_table("secagg_open", survivors, dev, "survivors")
+    nd = 0 if dropped is None else _secagg_table("secagg_open", dropped, dev, "dropped", allow_empty=True)
+    if nd == 0:
+        dropped = None
+    if ns + nd > SECAGG_MAX_CLIENTS:
+        raise ValueError(f"secagg_open: more than {SECAGG_MAX_CLIENTS} clients")
+    if not survivors.is_cuda and nd and set(survivors.tolist()) & set(dropped.tolist()):
+        raise ValueError("secagg_open: a client is both a survivor and dropped")
+    if P == 0:
+        return delta
+    seed, round = int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF
+    if not words.is_cuda:
+        ref.secagg_open(words, survivors, dropped, frac_bits, seed, round, delta)
+        return delta
+    check(_lib.kernels().ddl_secagg_open(ptr(words), ldw, R, P, ptr(survivors), ns, ptr(dropped), nd, frac_bits,
+                                         seed, round, ptr(delta), stream()), "secagg_open")
+    return delta
+
+
 SERVER_OPT_KINDS = ref.SERVER_OPT_KINDS  # sgdm (FedAvgM), adagrad, adam, yogi
 
 

@@ -600,6 +600,82 @@ def quantize_compress(rows, x, bank, slot_client, bits, seed, round, levels=None
             scales[g].copy_(s)
 
 
+# ----------------------------------------- secure aggregation (secagg.hip), int64 torch twins
+SECAGG_TAG = 0x9B05688C
+SECAGG_MAX_CLIENTS = 65536
+
+
+def secagg_pair_mask(P: int, a: int, b: int, seed: int, round: int):
+    """m(a, b, e) for e in [0, P), a <= b, as int64 holding 32-bit words: word e & 3 of
+    philox4x32(counter (Q_lo, Q_hi, (a << 16) | b, round), key (seed_lo ^ SECAGG_TAG, seed_hi))."""
+    q = torch.arange((P + 3) >> 2, dtype=torch.int64)
+    zero = torch.zeros_like(q)
+    r = philox4x32_t(q & _M32, q >> 32, zero + (((a << 16) | b) & _M32), zero + (round & _M32),
+                     (seed & _M32) ^ SECAGG_TAG, (seed >> 32) & _M32)
+    return torch.stack(r, 1).reshape(-1)[:P]
+
+
+def _secagg_signed_pair(P, i, j, seed, round):
+    """s_ij m(min, max, .) for i != j: +m for i < j, -m for i > j."""
+    m = secagg_pair_mask(P, min(i, j), max(i, j), seed, round)
+    return m if i < j else -m
+
+
+def _to_i32(t):
+    """int64 holding any integer -> its residue mod 2^32 as int32 bits."""
+    t = t & _M32
+    return torch.where(t >= 2 ** 31, t - 2 ** 32, t).to(torch.int32)
+
+
+def secagg_encode(rows, center, cs, n: int, frac_bits: int):
+    """-> (q [G, P] int64, sat [G] int64): the fixed-point updates of secagg_mask_kernel."""
+    G, P = rows.shape
+    lim = (2 ** 31 - 1) // n
+    q = torch.zeros(G, P, dtype=torch.int64)
+    sat = torch.zeros(G, dtype=torch.int64)
+    for g, k in enumerate(cs.tolist()):
+        if k == 0.0:
+            continue  # not read
+        d = rows[g] if center is None else rows[g] - center
+        p = cs[g] * d  # each rounded to fp32
+        r = torch.round(p.double() * float(1 << frac_bits))  # ties to even
+        nan = torch.isnan(r)
+        over = nan | (r.abs() > lim)
+        r = torch.where(nan, torch.zeros_like(r), r.clamp(-lim, lim))
+        q[g] = r.to(torch.int64)
+        sat[g] = int(over.sum())
+    return q, sat
+
+
+def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits, seed, round, words, sat):
+    G, P = rows.shape
+    ids, U = slot_client.tolist(), cohort.tolist()
+    q, over = secagg_encode(rows, center, cs, len(U), frac_bits)
+    for g, i in enumerate(ids):
+        y = q[g] + secagg_pair_mask(P, i, i, seed, round)
+        for j in U:
+            if j != i:
+                y = y + _secagg_signed_pair(P, i, j, seed, round)
+        words[g].copy_(_to_i32(y))
+    sat.copy_(over.to(torch.int32))
+
+
+def secagg_sum(words, out):
+    out.copy_(_to_i32(words.to(torch.int64).sum(0)))
+
+
+def secagg_open(words, survivors, dropped, frac_bits, seed, round, delta):
+    P = words.shape[1]
+    T = words.to(torch.int64).sum(0)
+    D = [] if dropped is None else dropped.tolist()
+    for i in survivors.tolist():
+        T = T - secagg_pair_mask(P, i, i, seed, round)
+        for d in D:
+            T = T - _secagg_signed_pair(P, i, d, seed, round)
+    # int32 -> fp32 rounds to nearest even; the power of two is exact
+    delta.copy_(_to_i32(T).to(torch.float32) * (1.0 / float(1 << frac_bits)))
+
+
 def mse_kl(xr, x, mu, lv, kl_w=1.0):
     mse = ((xr - x) ** 2).sum()
     kl = -0.5 * (1 + lv - mu * mu - lv.exp()).sum()
