@@ -34,6 +34,7 @@ import math
 import torch
 
 from ..ops import functional as Fn
+from ..runtime.staging import DeviceTables
 
 
 class MeanAggregator:
@@ -43,7 +44,7 @@ class MeanAggregator:
     def __init__(self, ordered: bool | None = None):
         import os
         self.ordered = (os.environ.get("DDL_FL_ORDERED_MEAN", "1") != "0") if ordered is None else bool(ordered)
-        self._ones: dict = {}
+        self._tables = DeviceTables()  # small device tensors built on the host: ones, weights, id tables
 
     def __call__(self, ctx, rows: torch.Tensor, coeffs: torch.Tensor, out: torch.Tensor):
         """rows [G_local, P] (strided ok), coeffs [G_local] -> out[P] = global weighted sum."""
@@ -67,10 +68,8 @@ class MeanAggregator:
             ipc.all_reduce_ordered(out)
             return out
         parts = ctx.all_gather_rows(out)  # [W, P]: every rank's partial, in rank order
-        key = (parts.shape[0], out.device)
-        ones = self._ones.get(key)
-        if ones is None:
-            ones = self._ones[key] = torch.ones(parts.shape[0], dtype=torch.float32, device=out.device)
+        W, dev = parts.shape[0], out.device
+        ones = self._tables.get(("ones", W, dev), lambda: torch.ones(W, dtype=torch.float32, device=dev))
         Fn.weighted_sum(parts, ones, out)  # x 1.0 is exact: a plain rank-order sum
         return out
 
@@ -118,39 +117,49 @@ class ClippedMean(MeanAggregator):
         self.weighting = weighting
         self.rounds = 0      # the noise stream's round: this aggregator's own call counter
         self.last_k = 0      # clients that reported in the last round (all ranks)
-        self._delta: dict = {}
-        self._uniform: dict = {}
         self._norms = None
 
     def __call__(self, ctx, rows: torch.Tensor, coeffs: torch.Tensor, out: torch.Tensor,
                  center: torch.Tensor | None = None, counts: list[int] | None = None):
         """rows [G_local, P], coeffs [G_local], center [P] or None (the rows are the updates) ->
         out[P] = center + sum_k c_k * clip(rows_k - center) (+ noise); out may be center."""
-        G, P = rows.shape
         if counts is None:
             if ctx.is_distributed and self.weighting == "uniform":
                 raise ValueError("uniform weighting over several ranks needs the per-rank client counts")
-            counts = [G]
-        K_r = int(sum(counts))
+            counts = [rows.shape[0]]
+        return self._clipped(ctx, rows, coeffs, out, center, int(sum(counts)))
+
+    def _clipped(self, ctx, rows, coeffs, out, center, K_r: int):
+        """The body for K_r reporting clients on all ranks; one without rows still reduces with the others."""
+        G, P = rows.shape
         dev = out.device
-        delta = self._delta.get((P, dev))
-        if delta is None:
-            delta = self._delta[(P, dev)] = torch.empty(P, dtype=torch.float32, device=dev)
-        if G == 0:
+        delta = self._tables.get(("delta", P, dev), lambda: torch.empty(P, dtype=torch.float32, device=dev))
+        cs = self._norms = None
+        if G:
+            rows, coeffs, cs = self._prepare(rows, coeffs, center, G, K_r, dev)
+        self._reduce(ctx, rows, center, cs, delta)
+        return self._finish(out, center, delta, K_r)
+
+    def _prepare(self, rows, coeffs, center, G, K_r, dev):
+        """-> (rows with unit inner stride, the weights in use, cs [G] = weight * clip factor)."""
+        if rows.stride(1) != 1:
+            rows = rows.contiguous()
+        if self.weighting == "uniform":
+            coeffs = self._tables.get(("uniform", G, K_r, dev),
+                                      lambda: torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev))
+        self._norms, cs = Fn.clip_scales(Fn.update_sqnorm(rows, center), coeffs, self.clip)
+        return rows, coeffs, cs
+
+    def _reduce(self, ctx, rows, center, cs, delta):
+        """delta = the sum of the scaled updates over all ranks; cs None: this rank has no rows."""
+        if cs is None:
             delta.zero_()
-            self._norms = None
         else:
-            if rows.stride(1) != 1:
-                rows = rows.contiguous()
-            if self.weighting == "uniform":
-                coeffs = self._uniform.get((G, K_r, dev))
-                if coeffs is None:
-                    coeffs = self._uniform[(G, K_r, dev)] = torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev)
-            sq = Fn.update_sqnorm(rows, center)
-            self._norms, cs = Fn.clip_scales(sq, coeffs, self.clip)
             Fn.clipped_sum(rows, center, cs, delta)
         self.cross_rank_sum(ctx, delta)
-        std = self.noise_multiplier * self.clip / K_r if K_r else 0.0
+
+    def _finish(self, out, center, delta, K_r):
+        std = self.noise_multiplier * self.clip / K_r if self.noise_multiplier > 0.0 and K_r else 0.0
         Fn.apply_update(out, center, delta, std, self.seed, self.rounds)
         self.rounds += 1
         self.last_k = K_r
@@ -214,9 +223,7 @@ class SecureMean(ClippedMean):
         self.aborted: list[int] = []
         self._round = None     # (cohort, survivors, dropped, this rank's clients) of the announced round
         self._uploads: dict = {}
-        self._tables: dict = {}
-        self._last = None
-        self._sat = None
+        self._last = self._sat = None
 
     def begin_round(self, cohort, survivors, clients) -> None:
         """The round's cohort (every sampled client), the survivors (those that report, on all
@@ -230,13 +237,7 @@ class SecureMean(ClippedMean):
         self._round = (cohort, survivors, [c for c in cohort if c not in alive], clients)
 
     def _table(self, ids, dev):
-        key = (tuple(ids), dev)
-        t = self._tables.get(key)
-        if t is None:
-            t = torch.tensor(ids, dtype=torch.int32, device=dev)
-            if len(self._tables) < 256:
-                self._tables[key] = t
-        return t
+        return self._tables.get((tuple(ids), dev), lambda: torch.tensor(ids, dtype=torch.int32, device=dev))
 
     def abort_round(self, out: torch.Tensor | None = None, center: torch.Tensor | None = None):
         """Too few survivors: nothing is opened, the model stays, the round is counted."""
@@ -253,8 +254,8 @@ class SecureMean(ClippedMean):
                  center: torch.Tensor | None = None, counts: list[int] | None = None):
         if self._round is None:
             raise RuntimeError("secagg: begin_round(cohort, survivors, clients) must announce the round")
-        cohort, survivors, dropped, clients = self._round
-        G, P = rows.shape
+        survivors, clients = self._round[1], self._round[3]
+        G = rows.shape[0]
         if len(clients) != G:
             raise ValueError(f"secagg: {G} rows for the {len(clients)} clients announced")
         K_r = len(survivors)
@@ -264,43 +265,31 @@ class SecureMean(ClippedMean):
             self.last_k = K_r
             self.abort_round(out, center)
             return out
-        dev = out.device
-        delta = self._delta.get((P, dev))
-        if delta is None:
-            delta = self._delta[(P, dev)] = torch.empty(P, dtype=torch.float32, device=dev)
-        slots = max(G, 1)
+        self._clipped(ctx, rows, coeffs, out, center, K_r)
+        self._round = None
+        return out
+
+    def _reduce(self, ctx, rows, center, cs, delta):
+        """The scaled updates go up masked; delta = what opening their sum over all ranks gives."""
+        cohort, survivors, dropped, clients = self._round
+        G, P = rows.shape
+        dev = delta.device
         up = self._uploads.get((P, dev))
-        if up is None or up.shape[0] < slots:
-            up = self._uploads[(P, dev)] = torch.empty(slots, P, dtype=torch.int32, device=dev)
-        if G == 0:
-            self._norms = self._last = self._sat = None
-        else:
-            if rows.stride(1) != 1:
-                rows = rows.contiguous()
-            if self.weighting == "uniform":
-                coeffs = self._uniform.get((G, K_r, dev))
-                if coeffs is None:
-                    coeffs = self._uniform[(G, K_r, dev)] = torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev)
-            sq = Fn.update_sqnorm(rows, center)
-            self._norms, cs = Fn.clip_scales(sq, coeffs, self.clip)
+        if up is None or up.shape[0] < max(G, 1):
+            up = self._uploads[(P, dev)] = torch.empty(max(G, 1), P, dtype=torch.int32, device=dev)
+        self._last = self._sat = None
+        if cs is not None:
             self._sat = torch.empty(G, dtype=torch.int32, device=dev)
             self._last = Fn.secagg_mask(rows, center, cs, self._table(clients, dev), self._table(cohort, dev),
                                         self.frac_bits, self.seed, self.rounds, up[:G], self._sat)
-        alive = self._table(survivors, dev)
-        gone = self._table(dropped, dev) if dropped else None
-        if not ctx.is_distributed:
-            Fn.secagg_open(up[:G], alive, gone, self.frac_bits, self.seed, self.rounds, delta)
-        else:
+        words = up[:G]
+        if ctx.is_distributed:
             part = torch.zeros(P, dtype=torch.int32, device=dev)
             if G:
-                Fn.secagg_sum(up[:G], part)
-            Fn.secagg_open(ctx.all_gather_rows(part), alive, gone, self.frac_bits, self.seed, self.rounds, delta)
-        std = self.noise_multiplier * self.clip / K_r if self.noise_multiplier > 0.0 else 0.0
-        Fn.apply_update(out, center, delta, std, self.seed, self.rounds)
-        self.rounds += 1
-        self.last_k = K_r
-        self._round = None
-        return out
+                Fn.secagg_sum(words, part)
+            words = ctx.all_gather_rows(part)
+        Fn.secagg_open(words, self._table(survivors, dev), self._table(dropped, dev) if dropped else None,
+                       self.frac_bits, self.seed, self.rounds, delta)
 
     @property
     def last_uploads(self):

@@ -20,7 +20,9 @@ import torch
 
 from ..ops import functional as Fn
 from ..runtime import dist as rdist
+from ..runtime.staging import DeviceTables, PinnedStager
 from ..utils.metrics import PhaseTimer
+from . import bank as banks
 from .aggregate import MeanAggregator, aggregate_into, make_aggregator
 from .compress import make_compressor
 from .local import LocalTrainer
@@ -57,7 +59,7 @@ class FederatedBase:
         self.compressor = make_compressor(compressor, **(compressor_kwargs or {})) \
             if isinstance(compressor, str) else compressor
         self._uplink: list = []
-        self._slot_tables: dict = {}
+        self._slot_tables, self._coeff_cache = DeviceTables(), DeviceTables()
         self.ctx = ctx or rdist.context()
         self.dev = self.ctx.device
         self.data = train_data
@@ -113,7 +115,6 @@ class FederatedBase:
         # samples, plans and enqueues round r+1 while the GPU still executes round r. For
         # throughput runs (bench.py); run() keeps the reference's per-round timing.
         self.sync_rounds = True
-        self._coeff_cache: dict = {}
 
     def _sample(self):
         chosen = self.rng.choice(self.N, self.K, replace=False)
@@ -147,9 +148,8 @@ class FederatedBase:
               "sim_time": self.sim_time,
               "algorithm": self.algorithm, "N": self.N, "K": self.K, "seed": self.seed,
               "param_layout": self.net.store.param_layout()}
-        for name in ("g_global",):
-            if hasattr(self, name):
-                sd[name] = getattr(self, name).detach().cpu().clone()
+        if hasattr(self, "g_global"):
+            sd["g_global"] = self.g_global.detach().cpu().clone()
         if self.attack is not None:
             sd["attack"] = self.attack.state_dict()
         if hasattr(self.aggregator, "state_dict"):  # e.g. ClippedMean's noise round counter
@@ -214,6 +214,25 @@ class FederatedBase:
         mine = [int(c) for c in chosen[self.ctx.rank::self.W]]
         counts = [len(chosen[i::self.W]) for i in range(self.W)]
         return mine, counts
+
+    def _coeffs(self, mine, total):
+        """Device tensor of the n_k / n weights of my clients; cached per (clients, total), since
+        building it from a host list is a blocking copy."""
+        return self._coeff_cache.get((tuple(mine), total), lambda: torch.tensor(
+            [self.counts[c] / total for c in mine], dtype=torch.float32, device=self.dev))
+
+    def _begin_round(self):
+        """Sample the round and tell the aggregator -> (chosen, mine, counts per rank, total samples),
+        or None when every sampled client dropped out: the server model stays, the round is counted."""
+        chosen = self._sample()
+        mine, self._counts = self._assign(chosen)  # the counts are kept for the hooks that gather over the ranks
+        self._announce(chosen, mine)
+        if len(chosen) == 0:
+            self.round_idx += 1
+            if self.compressor is not None:
+                self._uplink.append(0)
+            return None
+        return chosen, mine, self._counts, float(sum(self.counts[int(c)] for c in chosen))
 
     def _row_keys(self, counts):
         """Each rank-major client row's position in the round's `chosen` order (round-robin
@@ -286,10 +305,7 @@ class FederatedBase:
 
 class FedAvg(FederatedBase):
     algorithm = "FedAvg"
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.trainer = None
+    trainer = None  # the LocalTrainer, built in the first round
 
     def _trainer(self, mine):
         lt = None
@@ -320,74 +336,39 @@ class FedAvg(FederatedBase):
         if self.compressor is not None:
             self._compress(mine, chosen)
 
-    def _slot_table(self, ids):
-        """Device int32 table of the slots' client ids; cached like the coefficients."""
-        key = tuple(ids)
-        t = self._slot_tables.get(key)
-        if t is None:
-            t = torch.tensor(ids, dtype=torch.int32, device=self.dev)
-            if len(self._slot_tables) < 256:
-                self._slot_tables[key] = t
-        return t
-
     def _compress(self, mine, chosen):
         """Slot g's row becomes what the server decodes from client mine[g]'s compressed upload; the
         client's error row takes the residual. BN buffers stay dense. On several ranks the bank is
         replicated: the round's new rows are all-gathered and written by client id, as Scaffold's."""
         comp, st, G = self.compressor, self.net.store, len(mine)
         P, dense = self.w_global.numel(), 4 * self.b_global.numel() * len(chosen)
-        dist_ = self.ctx.is_distributed
-        counts = [len(chosen[w::self.W]) for w in range(self.W)]
         with self.timer("compress"):
             nnz = None
             if G:
                 ids = Fn.check_slot_clients(mine, self.N)  # the table is validated here, where it is built
-                nnz = comp.apply(st.data[:G], self.w_global, self._slot_table(ids))
+                table = self._slot_tables.get(tuple(ids), lambda: torch.tensor(ids, dtype=torch.int32, device=self.dev))
+                nnz = comp.apply(st.data[:G], self.w_global, table)
             else:
                 comp.skip()  # every rank counts the round: the draws do not depend on the placement
             if comp.name == "topk":
                 send = torch.zeros(self.slots, dtype=torch.int32, device=self.dev)
                 if G:
                     send[:G] = nnz
-                self._uplink.append((self.ctx.all_gather_rows(send), counts, dense))
+                self._uplink.append((self.ctx.all_gather_rows(send), self._counts, dense))
             else:
                 self._uplink.append(len(chosen) * comp.uplink_bytes(P) + dense)
-            if dist_ and comp.bank is not None:
-                send = torch.zeros(self.slots, P, dtype=torch.float32, device=self.dev)
-                if G:
-                    send[:G] = comp.bank[torch.as_tensor(mine, dtype=torch.int64, device=self.dev)]
-                got = self.ctx.all_gather_rows(send)  # [W, slots, P]
-                for w in range(self.W):
-                    theirs = [int(c) for c in chosen[w::self.W]]
-                    if theirs and w != self.ctx.rank:
-                        comp.bank[torch.as_tensor(theirs, dtype=torch.int64, device=self.dev)] = got[w, :len(theirs)]
-
-    def _coeffs(self, mine, total):
-        """Device tensor of the n_k / n weights of my clients; cached per (clients, total), since
-        building it from a host list is a blocking copy."""
-        key = (tuple(mine), total)
-        t = self._coeff_cache.get(key)
-        if t is None:
-            t = torch.tensor([self.counts[c] / total for c in mine], dtype=torch.float32, device=self.dev)
-            if len(self._coeff_cache) < 256:
-                self._coeff_cache[key] = t
-        return t
+            if comp.bank is not None:
+                banks.replicate_rows(self.ctx, comp.bank, chosen, mine, self.slots)
 
     def round(self):
         if self.sync_rounds:
             _sync(self.dev)
         t0 = time.perf_counter()
-        chosen = self._sample()
-        if len(chosen) == 0:  # every sampled client dropped out: the server model stays
-            self.round_idx += 1
-            self._announce(chosen, [])
-            if self.compressor is not None:
-                self._uplink.append(0)
+        began = self._begin_round()
+        if began is None:
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
-        mine, counts = self._assign(chosen)
-        self._announce(chosen, mine)
+        chosen, mine, counts, total = began
         G = len(mine)
-        total = float(sum(self.counts[int(c)] for c in chosen))
         r = self.round_idx
         with self.timer("download"):
             self._download(G)
@@ -494,7 +475,8 @@ class Scaffold(FedAvg):
         self.slot_client = torch.zeros(self.slots, dtype=torch.int32, device=self.dev)
         self._inv_klr = torch.zeros(self.slots, dtype=torch.float32, device=self.dev)
         self._dc = torch.zeros(P, dtype=torch.float32, device=self.dev)
-        self._staging: dict = {}
+        self._stagers = {"slot_client": PinnedStager(self.slot_client.shape, torch.int32),
+                         "inv_klr": PinnedStager(self._inv_klr.shape, torch.float32)}
 
     def _trainer_kwargs(self) -> dict:
         return {"control": (self.c_global, self.c_bank, self.slot_client)}
@@ -506,25 +488,8 @@ class Scaffold(FedAvg):
         return self.E * (math.ceil(n / B) if B > 0 else 1)
 
     def _stage(self, name: str, values: np.ndarray, out: torch.Tensor):
-        """Host values -> the first len(values) entries of the persistent device buffer ``out``,
-        without a blocking copy: double-buffered pinned staging, as LocalTrainer._upload."""
-        n = len(values)
-        if out.device.type != "cuda":
-            out[:n].copy_(torch.from_numpy(values))
-            return
-        slots = self._staging.get(name)
-        if slots is None:
-            slots = self._staging[name] = [[torch.empty(out.shape, dtype=out.dtype, pin_memory=True), None]
-                                           for _ in range(2)] + [0]
-        slots[2] ^= 1
-        buf, ev = slots[slots[2]]
-        if ev is not None:
-            ev.synchronize()  # the copy that last read this buffer (two rounds ago) is done
-        buf.numpy()[:n] = values
-        out[:n].copy_(buf[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        slots[slots[2]][1] = ev
+        """Host values -> out[:len(values)] of a persistent device buffer, without a blocking copy."""
+        self._stagers[name].put(values, out[:len(values)])
 
     def _before_local(self, mine):
         ids = Fn.check_slot_clients(mine, self.N)  # the table is validated here, where it is built
@@ -534,8 +499,7 @@ class Scaffold(FedAvg):
         self._stage("inv_klr", np.asarray(inv, dtype=np.float32), self._inv_klr)
 
     def _after_local(self, mine, chosen):
-        G = len(mine)
-        st = self.net.store
+        G, st = len(mine), self.net.store
         dist_ = self.ctx.is_distributed
         with self.timer("control"):
             if G:
@@ -547,30 +511,19 @@ class Scaffold(FedAvg):
                 return
             self.mean.cross_rank_sum(self.ctx, self._dc)
             self.c_global.add_(self._dc)
-            # every rank's new rows, written into every bank by client id (comm-bound: plain indexing)
-            send = torch.zeros(self.slots, self.c_bank.shape[1], dtype=torch.float32, device=self.dev)
-            if G:
-                send[:G] = self.c_bank[torch.as_tensor(mine, dtype=torch.int64, device=self.dev)]
-            got = self.ctx.all_gather_rows(send)  # [W, slots, P]
-            for w in range(self.W):
-                theirs = [int(c) for c in chosen[w::self.W]]
-                if theirs and w != self.ctx.rank:
-                    self.c_bank[torch.as_tensor(theirs, dtype=torch.int64, device=self.dev)] = got[w, :len(theirs)]
+            banks.replicate_rows(self.ctx, self.c_bank, chosen, mine, self.slots)
 
     def state_dict(self) -> dict:
         sd = super().state_dict()
         sd["c_global"] = self.c_global.detach().cpu().clone()
-        sd["c_bank"] = self.c_bank.detach().cpu().clone()
+        sd["c_bank"] = banks.bank_state(self.c_bank)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         super().load_state_dict(sd)
         fix = self._layout_fix(sd)
         self.c_global.copy_(fix(sd["c_global"]).to(self.dev))
-        bank = sd["c_bank"]
-        if bank.shape[0] != self.N:
-            raise ValueError(f"checkpoint holds {bank.shape[0]} control variates, this federation has {self.N} clients")
-        self.c_bank.copy_(fix(bank).to(self.dev))
+        banks.load_bank(self.c_bank, sd["c_bank"], fix, "control variates")
 
 
 class FedSGD(FederatedBase):
@@ -593,15 +546,11 @@ class FedSGD(FederatedBase):
     def round(self):
         _sync(self.dev)
         t0 = time.perf_counter()
-        chosen = self._sample()
-        if len(chosen) == 0:
-            self.round_idx += 1
-            self._announce(chosen, [])
+        began = self._begin_round()
+        if began is None:
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
-        mine, counts = self._assign(chosen)
-        self._announce(chosen, mine)
+        _, mine, counts, total = began
         G = len(mine)
-        total = float(sum(self.counts[int(c)] for c in chosen))
         self._download(G)
         st, net = self.net.store, self.net
         samples = 0
@@ -626,8 +575,7 @@ class FedSGD(FederatedBase):
         if self.attack is not None and G:
             # model-poisoning attacks act on the reported gradient ("update" = -grad direction)
             self.attack.poison_updates(st.grad[:G], torch.zeros_like(self.w_global), mine)
-        coeffs = torch.tensor([self.counts[c] / total for c in mine], dtype=torch.float32,
-                              device=self.dev)
+        coeffs = self._coeffs(mine, total)
         aggregate_into(self.aggregator, self.ctx, st.grad[:G], coeffs, self.g_global, center=None,  # the updates
                        counts=counts, keys=self._row_keys(counts))                                  # are the gradients
         # server SGD step (no momentum, as the reference's SGD(lr))

@@ -22,6 +22,7 @@ import math
 import torch
 
 from ..ops import functional as Fn
+from .bank import bank_state, load_bank
 
 BUCKET = 256
 
@@ -63,8 +64,7 @@ class Compressor:
         raise NotImplementedError
 
     def state_dict(self) -> dict:
-        return {"name": self.name, "round": self.round,
-                "bank": None if self.bank is None else self.bank.detach().cpu().clone()}
+        return {"name": self.name, "round": self.round, "bank": bank_state(self.bank)}
 
     def load_state_dict(self, sd: dict, fix=lambda t: t) -> None:
         if sd["name"] != self.name or (sd["bank"] is None) != (self.bank is None):
@@ -73,10 +73,7 @@ class Compressor:
                              f"(bank: {self.bank is not None})")
         self.round = int(sd["round"])
         if self.bank is not None:
-            if sd["bank"].shape[0] != self.bank.shape[0]:
-                raise ValueError(f"checkpoint holds {sd['bank'].shape[0]} error rows, this federation has "
-                                 f"{self.bank.shape[0]} clients")
-            self.bank.copy_(fix(sd["bank"]).to(self.bank.device))
+            load_bank(self.bank, sd["bank"], fix, "error rows")
 
 
 class TopK(Compressor):

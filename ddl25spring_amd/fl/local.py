@@ -20,6 +20,7 @@ import torch
 from .. import optim
 from ..data.split import plan_epoch
 from ..runtime.graphs import CAPTURE_MODE
+from ..runtime.staging import PinnedStager
 
 
 # Direct SGD (default on the GPU for plain SGD): the conv / Linear weights' WGRAD launches add -lr * dW
@@ -76,11 +77,7 @@ class LocalTrainer:
         self._graphs: dict = {}
         self._next: dict = {}
         self.last_loss = None
-        # double-buffered pinned staging of the round's batch plan: the host->device copy is then
-        # truly asynchronous, so with FederatedBase.sync_rounds off the host plans and enqueues
-        # round r+1 while the GPU still runs round r
-        self._pinned: dict = {}
-        self._pin_slot = 0
+        self._stagers: dict = {}  # pinned stagers of the round's batch plan, by plan shape
 
     # ---------------------------------------------------------------- one step (eager)
     def _step(self, idx, g0: int, g1: int):
@@ -215,22 +212,8 @@ class LocalTrainer:
         return out
 
     def _upload(self, plan: np.ndarray, dev) -> torch.Tensor:
-        if dev.type != "cuda":
-            return torch.from_numpy(plan).to(dev)
-        slots = self._pinned.get(plan.shape)
-        if slots is None:
-            slots = [[torch.empty(plan.shape, dtype=torch.int32, pin_memory=True), None] for _ in range(2)]
-            self._pinned[plan.shape] = slots
-        self._pin_slot ^= 1
-        buf, ev = slots[self._pin_slot]
-        if ev is not None:
-            ev.synchronize()  # the copy that last read this buffer (two uploads ago) is done
-        buf.numpy()[...] = plan
-        out = buf.to(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        slots[self._pin_slot][1] = ev
-        return out
+        stager = self._stagers.setdefault(plan.shape, PinnedStager(plan.shape, torch.int32))  # pins on first use
+        return stager.put(plan, dev)
 
     def _run_plan(self, plan: np.ndarray, g0: int, g1: int) -> int:
         dev = self.net.device

@@ -1242,7 +1242,7 @@ def _sgd_corrected_step(name, correction, term, p, g, mom, shadow, ref_row, lr, 
     a.p, a.g, a.mom, a.shadow = ptr(p), ptr(g), ptr(mom), ptr(shadow)
     a.ref, a.bank, a.slot_client = ptr(ref_row), ptr(bank), ptr(slot_client)
     a.rows, a.P = p.shape
-    a.ld = p.shape[1] if bank is None or bank.shape[0] <= 1 else bank.stride(0)
+    a.ld = _row_ld(bank, p.shape[1], lone=p.shape[1])
     a.lr, a.wd, a.momentum, a.dampening, a.grad_scale, a.mu = lr, wd, momentum, dampening, grad_scale, mu
     a.nesterov, a.first_step, a.correction = int(nesterov), int(first_step), correction
     check(_lib.kernels().ddl_sgd_corrected(ctypes.byref(a), stream()), name)
@@ -1269,16 +1269,28 @@ def check_slot_clients(ids, n_clients: int):
     return ids
 
 
-def _scaffold_bank_check(name, P, c, bank, slot_client, G):
-    assert c.dtype == torch.float32 and c.is_contiguous() and c.numel() == P
-    assert bank.dtype == torch.float32 and bank.dim() == 2 and bank.shape[1] == P
-    assert bank.shape[0] == 1 or bank.stride(0) >= P
-    assert slot_client.dtype == torch.int32 and slot_client.dim() == 1 and slot_client.numel() == G
-    assert slot_client.device == bank.device == c.device
-    if not slot_client.is_cuda:  # a host table is checked here; a device table where it was built
-        check_slot_clients(slot_client.tolist(), bank.shape[0])
-    if bank.is_cuda:
-        assert bank.stride(1) == 1 and slot_client.is_contiguous(), f"{name}: unit inner strides are needed"
+def _row_ld(t, P: int, lone=None) -> int:
+    """The leading stride of rows t [R, P] (or None) for a launcher. A single row's stride is never
+    used: a multiple of 4 keeps the 16-B path open for any P (``lone``: a caller's own value)."""
+    if t is not None and t.shape[0] > 1:
+        return t.stride(0)
+    return (P + 3) // 4 * 4 if lone is None else lone
+
+
+def _bank_table_check(name, P, G, bank, slot_client, dev):
+    """The clients' bank [N, P] (fp32, rows may be strided) and the int32 table slot_client [G] of the
+    slots' rows in it, on ``dev``, either or none. A host table's contents are checked here; a
+    device table's where it was built."""
+    if slot_client is not None:
+        assert slot_client.dtype == torch.int32 and slot_client.dim() == 1 and slot_client.numel() == G
+        assert slot_client.device == dev and (slot_client.is_contiguous() or not slot_client.is_cuda)
+    if bank is not None:
+        assert slot_client is not None, f"{name}: a bank needs the slot table"
+        assert bank.dtype == torch.float32 and bank.dim() == 2 and bank.shape[1] == P and bank.device == dev
+        assert bank.shape[0] == 1 or bank.stride(0) >= P
+        assert bank.stride(1) == 1 or not bank.is_cuda, f"{name}: unit inner strides are needed"
+        if not slot_client.is_cuda:
+            check_slot_clients(slot_client.tolist(), bank.shape[0])
 
 
 def sgd_scaffold_step(p, g, mom, shadow, c, bank, slot_client, lr, wd=0.0, momentum=0.0, dampening=0.0,
@@ -1287,8 +1299,8 @@ def sgd_scaffold_step(p, g, mom, shadow, c, bank, slot_client, lr, wd=0.0, momen
     ``c - bank[slot_client[row]]`` with the server control variate c [P] and the clients' control
     variates bank [N, P] (rows may be strided), read in place through the int32 table slot_client
     [G] on the rows' device."""
-    assert p.dim() == 2
-    _scaffold_bank_check("sgd_scaffold_step", p.shape[1], c, bank, slot_client, p.shape[0])
+    assert p.dim() == 2 and c.dtype == torch.float32 and c.is_contiguous() and c.numel() == p.shape[1]
+    _bank_table_check("sgd_scaffold_step", p.shape[1], p.shape[0], bank, slot_client, c.device)
     _sgd_corrected_step("sgd_scaffold_step", _lib.SGD_CONTROL, lambda: c.reshape(1, -1) - bank[slot_client.long()],
                         p, g, mom, shadow, c, lr, wd, momentum, dampening, nesterov, first_step, grad_scale,
                         bank=bank, slot_client=slot_client)
@@ -1306,8 +1318,8 @@ def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c=F
     nothing. All fp32, every operation rounded on its own; (3G + 3) P floats moved."""
     G, P = rows.shape
     assert rows.dtype == torch.float32 and G >= 1
-    _scaffold_bank_check("scaffold_finish", P, c, bank, slot_client, G)
-    for t in (x, dc):
+    _bank_table_check("scaffold_finish", P, G, bank, slot_client, c.device)
+    for t in (x, c, dc):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == P
     assert inv_klr.dtype == torch.float32 and inv_klr.numel() == G and inv_klr.device == rows.device
     if P == 0:
@@ -1316,8 +1328,7 @@ def scaffold_finish(rows, x, c, bank, slot_client, inv_klr, inv_n, dc, apply_c=F
         ref.scaffold_finish(rows, x, c, bank, slot_client, inv_klr, float(inv_n), dc, apply_c)
         return dc
     assert rows.stride(1) == 1 and inv_klr.is_contiguous()
-    ld = bank.stride(0) if bank.shape[0] > 1 else P
-    ldy = rows.stride(0) if G > 1 else P
+    ld, ldy = _row_ld(bank, P, lone=P), _row_ld(rows, P, lone=P)
     check(_lib.kernels().ddl_scaffold_finish(ptr(rows), ldy, ptr(x), ptr(c), ptr(bank), ld, ptr(slot_client),
                                              ptr(inv_klr), G, float(inv_n), ptr(dc), P, int(bool(apply_c)),
                                              stream()), "scaffold_finish")
@@ -1329,22 +1340,9 @@ def _compress_check(name, rows, x, bank, slot_client):
     G, P = rows.shape
     assert rows.dtype == torch.float32 and G >= 1
     assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == P and x.device == rows.device
-    if slot_client is not None:
-        assert slot_client.dtype == torch.int32 and slot_client.dim() == 1 and slot_client.numel() == G
-        assert slot_client.device == rows.device
-    if bank is not None:
-        assert slot_client is not None, f"{name}: a bank needs the slot table"
-        assert bank.dtype == torch.float32 and bank.dim() == 2 and bank.shape[1] == P and bank.device == rows.device
-        assert bank.shape[0] == 1 or bank.stride(0) >= P
-        if not slot_client.is_cuda:  # a host table is checked here; a device table where it was built
-            check_slot_clients(slot_client.tolist(), bank.shape[0])
-    if rows.is_cuda:
-        assert rows.stride(1) == 1 and (bank is None or bank.stride(1) == 1), f"{name}: unit inner strides are needed"
-        assert slot_client is None or slot_client.is_contiguous()
-    # a single row's stride is never used: a multiple of 4 keeps the 16-B path open for any P
-    ldy = rows.stride(0) if G > 1 else (P + 3) // 4 * 4
-    ld = (P + 3) // 4 * 4 if bank is None or bank.shape[0] <= 1 else bank.stride(0)
-    return G, P, ldy, ld
+    _bank_table_check(name, P, G, bank, slot_client, rows.device)
+    assert rows.stride(1) == 1 or not rows.is_cuda, f"{name}: unit inner strides are needed"
+    return G, P, _row_ld(rows, P), _row_ld(bank, P)
 
 
 def topk_compress(rows, x, bank, slot_client, k: int, nnz):
@@ -1441,12 +1439,11 @@ def _secagg_table(name, t, dev, what, allow_empty=False):
     return t.numel()
 
 
-def _secagg_words(name, words, dev):
-    assert words.dtype == torch.int32 and words.dim() == 2 and words.device == dev, f"{name}: words"
-    R, P = words.shape
-    assert R >= 1 and (P == 0 or words.stride(1) == 1) and (R == 1 or words.stride(0) >= P), f"{name}: words"
-    # a single row's stride is never used: a multiple of 4 keeps the 16-B path open for any P
-    return R, P, words.stride(0) if R > 1 else (P + 3) // 4 * 4
+def _secagg_rows(name, t, dev, dtype=torch.int32, what="words"):
+    assert t.dtype == dtype and t.dim() == 2 and t.device == dev, f"{name}: {what}"
+    R, P = t.shape
+    assert R >= 1 and (P == 0 or t.stride(1) == 1) and (R == 1 or t.stride(0) >= P), f"{name}: {what}"
+    return R, P, _row_ld(t, P)
 
 
 # the mask kernel's form for 2..8 local rows: a thread holds its quad of every row and a pair of two
@@ -1467,10 +1464,9 @@ def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits: int, seed: int
     with cs[g] == 0 is not read: its words are the bare masks. center None: the rows are the updates.
     ``pair_shared`` picks the kernel's form (None: ``SECAGG_PAIR_SHARED``); both give the same bits.
     Nothing is copied to the host. -> words."""
-    G, P = rows.shape
     dev = rows.device
     frac_bits = _secagg_bits("secagg_mask", frac_bits)
-    assert rows.dtype == torch.float32 and G >= 1 and (P == 0 or rows.stride(1) == 1)
+    G, P, ld = _secagg_rows("secagg_mask", rows, dev, torch.float32, "rows")
     assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == P
                               and center.device == dev)
     assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == G and cs.device == dev
@@ -1478,7 +1474,7 @@ def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits: int, seed: int
     assert _secagg_table("secagg_mask", slot_client, dev, "slot_client") == G
     if not cohort.is_cuda and not set(slot_client.tolist()) <= set(cohort.tolist()):
         raise ValueError("secagg_mask: a slot's client is not in the cohort")
-    R, Pw, ldw = _secagg_words("secagg_mask", words, dev)
+    R, Pw, ldw = _secagg_rows("secagg_mask", words, dev)
     assert (R, Pw) == (G, P), "secagg_mask: words must be [G, P]"
     assert sat.dtype == torch.int32 and sat.numel() == G and sat.is_contiguous() and sat.device == dev
     if P == 0:
@@ -1488,8 +1484,6 @@ def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits: int, seed: int
     if not rows.is_cuda:
         ref.secagg_mask(rows, center, cs, slot_client, cohort, frac_bits, seed, round, words, sat)
         return words
-    ld = rows.stride(0) if G > 1 else (P + 3) // 4 * 4
-    assert ld >= P
     check(_lib.kernels().ddl_secagg_mask(ptr(rows), ld, ptr(center), ptr(cs), ptr(slot_client), G, P, ptr(cohort), n,
                                          frac_bits, seed, round, ptr(words), ldw, ptr(sat),
                                          int(SECAGG_PAIR_SHARED if pair_shared is None else bool(pair_shared)),
@@ -1500,7 +1494,7 @@ def secagg_mask(rows, center, cs, slot_client, cohort, frac_bits: int, seed: int
 def secagg_sum(words, out):
     """out [P] int32 = the sum mod 2^32 of the rows of words [R, P] int32 (secagg.hip): a rank's
     partial of the masked uploads it holds."""
-    R, P, ldw = _secagg_words("secagg_sum", words, out.device)
+    R, P, ldw = _secagg_rows("secagg_sum", words, out.device)
     assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == P
     if P == 0:
         return out
@@ -1519,7 +1513,7 @@ def secagg_open(words, survivors, dropped, frac_bits: int, seed: int, round: int
     the cohort the uploads were masked against, or the result is noise. -> delta."""
     dev = delta.device
     frac_bits = _secagg_bits("secagg_open", frac_bits)
-    R, P, ldw = _secagg_words("secagg_open", words, dev)
+    R, P, ldw = _secagg_rows("secagg_open", words, dev)
     assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == P
     ns = _secagg_table("secagg_open", survivors, dev, "survivors")
     nd = 0 if dropped is None else _secagg_table("secagg_open", dropped, dev, "dropped", allow_empty=True)
