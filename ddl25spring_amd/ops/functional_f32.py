@@ -824,6 +824,13 @@ def bn_bwd_reduce_part(dy, ymask, x, mean, rstd):
 
 
 def bn_stats(x):
+    """Standalone forward statistics of x [G, ..., C] -> SlotStats with rows == 0: per-block
+    (sum, sum of squares) slots in fp32, folded in double by bn_finalize as var = E[x^2] - mean^2.
+    Single-pass by design (one read of x), so the variance keeps only what fp32 keeps of x^2: rstd is
+    within 2e-6 of float64 where |mean| < std, but at |mean| / std = 100 rstd is off by 5.1e-4 (measured,
+    tests/test_bn_f32_oracle_gpu.py::test_bn_stats_single_pass_error_at_shifted_mean), and one row
+    per channel is the limit case. The conv epilogues' two-pass (sum, M2) slots (rows > 0) stay
+    within 3e-6 there; callers whose activations may be far from zero-mean want those."""
     G, C = x.shape[0], x.shape[-1]
     M = x[0].numel() // C
     st = SlotStats()

@@ -218,6 +218,10 @@ def _bn_ref(c, gamma, beta, eps=1e-5):
 
 
 def test_bn_f32_forward_backward(cuda):
+    """Fn.bn_stats -> bn_finalize -> bn_apply -> bn_backward at one shape. The statistics come from
+    bn_stats, so bn_finalize takes its sum / sum-of-squares branch (SlotStats.rows == 0, slot_fold);
+    the branch the network's convs feed — per-tile (sum, M2) slots merged by Chan's formula,
+    rows > 0 — is covered by test_bn_f32_oracle_gpu.py::test_conv_slots_finalize."""
     torch.manual_seed(4)
     G, M, C = 2, 777, 64
     c = torch.randn(G, M, C, device=cuda) * 2 + 0.5
