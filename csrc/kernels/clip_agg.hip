@@ -7,6 +7,8 @@
 //                       cs[k] = 0 for a row whose squared norm is NaN / Inf
 //   ddl_clipped_sum   : delta[i] (+)= sum_k cs[k] * fl32(x_ki - c_i), rows with cs[k] == 0 not read
 //   ddl_apply_update  : w[i] = c[i] + delta[i] + std * z_i, z_i ~ N(0, 1) from Philox
+//   ddl_cc_step       : one centered-clipping iteration, v += sum_k cs[k] * fl32(x_k - ctr), fused
+//                       with the next iteration's squared norms (up to 16 rows, see there)
 //
 // All four stream: two reads of the client rows (norms, then the sum), no LDS tiling, no scratch,
 // no float atomics, and no block waits for another: the per-block partial squared norms go out with
@@ -154,6 +156,110 @@ DDL_API int ddl_clipped_sum(const float* X, long long ld, const float* center, c
   hipLaunchKernelGGL(clipped_sum_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, X, ld,
                      center, cs, G, n, out, accumulate);
   return (int)hipGetLastError();
+}
+
+// One iteration of centered clipping (Karimireddy et al. 2021) in ONE read of the rows:
+//   v_out[i]   = v_in[i] + sum_k cs[k] * fl32(x_ki - ctr_in[i])   (clipped_sum_kernel's order and
+//                roundings, rows with cs[k] == 0 not read)
+//   ctr_out[i] = c[i] + v_out[i]                                   (v_out[i] without a centre)
+// and, with NORMS, while the row quads are still in registers, the next iteration's squared norms
+// part[k][block] = sum_i fl32(x_ki - ctr_out[i])^2 in double: wave shuffle, LDS, plain stores, folded
+// by sqnorm_fold_kernel. A row that was not read gets +inf partials: its next cs is 0 again.
+// v_out may be v_in and ctr_out may be ctr_in or c: a thread reads its coordinates of every operand
+// before it writes them, and no other thread touches those coordinates.
+constexpr int CC_MAX_ROWS = 16;
+constexpr int CC_GRID_CAP = 2048;  // every block ends in up to 16 reductions: few long blocks
+
+template <int RC, bool NORMS>
+__global__ __launch_bounds__(256) void cc_step_kernel(const float* __restrict__ X, long long ld, const float* c,
+                                                      const float* ctr_in, const float* v_in,
+                                                      const float* __restrict__ cs, int G, long long n,
+                                                      float* v_out, float* ctr_out, double* __restrict__ part) {
+  __shared__ double red[RC][4];
+  const bool vec = (ld % 4) == 0 && (((uintptr_t)X | (uintptr_t)c | (uintptr_t)ctr_in | (uintptr_t)v_in |
+                                      (uintptr_t)v_out | (uintptr_t)ctr_out) & 15) == 0;
+  float k[RC];
+  double sq[RC];
+#pragma unroll
+  for (int g = 0; g < RC; ++g) {
+    k[g] = g < G ? cs[g] : 0.f;
+    sq[g] = 0.0;
+  }
+  quad_stream(n, vec, [&](long long e, auto w) {
+#pragma clang fp contract(off)
+    constexpr int W = decltype(w)::value;
+    fvec<W> acc = ldv<W>(v_in + e);
+    const fvec<W> m = ldv<W>(ctr_in + e);
+    fvec<W> x[RC];
+#pragma unroll
+    for (int g = 0; g < RC; ++g) {
+      if (k[g] == 0.f) continue;  // dropped row, zero weight or g >= G: not read
+      x[g] = ldv<W>(X + g * ld + e);
+#pragma unroll
+      for (int i = 0; i < W; ++i) acc[i] = acc[i] + k[g] * (x[g][i] - m[i]);
+    }
+    fvec<W> o = acc;
+    if (c) {
+      const fvec<W> b = ldv<W>(c + e);
+#pragma unroll
+      for (int i = 0; i < W; ++i) o[i] = b[i] + acc[i];
+    }
+    stv<W>(v_out + e, acc);
+    stv<W>(ctr_out + e, o);
+    if constexpr (NORMS) {
+#pragma unroll
+      for (int g = 0; g < RC; ++g) {
+        if (k[g] == 0.f) continue;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+          const float d = x[g][i] - o[i];
+          sq[g] = sq[g] + (double)d * (double)d;
+        }
+      }
+    }
+  });
+  if constexpr (NORMS) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int g = 0; g < RC; ++g) {
+      double a = sq[g];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+      if (lane == 0) red[g][wid] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < RC && (int)threadIdx.x < G) {
+      const int g = threadIdx.x;
+      const double s = (red[g][0] + red[g][1]) + (red[g][2] + red[g][3]);
+      part[(long long)g * gridDim.x + blockIdx.x] = cs[g] == 0.f ? (double)INFINITY : s;
+    }
+  }
+}
+
+// blocks of a `ddl_cc_step` launch: the doubles of scratch it needs per row
+DDL_API int ddl_cc_step_blocks(long long n) { return n < 1 ? 0 : grid_for((n + 3) / 4, 256, CC_GRID_CAP); }
+
+// part == null: the last step, no norms. Otherwise sq[G] takes the folded squared norms.
+DDL_API int ddl_cc_step(const float* X, long long ld, const float* c, const float* ctr_in, const float* v_in,
+                        const float* cs, int G, long long n, float* v_out, float* ctr_out, double* part,
+                        long long part_cap, double* sq, hipStream_t s) {
+  if (G < 1 || G > CC_MAX_ROWS || n < 1) return (int)hipErrorInvalidValue;
+  const int bx = ddl_cc_step_blocks(n);
+  if (part && (part_cap < (long long)G * bx || !sq)) return (int)hipErrorInvalidValue;
+#define CC_CASE(RC_) \
+  if (G <= RC_) { \
+    if (part) \
+      hipLaunchKernelGGL((cc_step_kernel<RC_, true>), dim3(bx), dim3(256), 0, s, X, ld, c, ctr_in, v_in, cs, G, \
+                         n, v_out, ctr_out, part); \
+    else \
+      hipLaunchKernelGGL((cc_step_kernel<RC_, false>), dim3(bx), dim3(256), 0, s, X, ld, c, ctr_in, v_in, cs, G, \
+                         n, v_out, ctr_out, part); \
+    if (part) hipLaunchKernelGGL(sqnorm_fold_kernel, dim3(G), dim3(256), 0, s, part, bx, G, sq); \
+    return (int)hipGetLastError(); \
+  }
+  CC_CASE(4) CC_CASE(8) CC_CASE(16)
+#undef CC_CASE
+  return (int)hipErrorInvalidValue;
 }
 
 // Gaussian noise of the server update: z_i is a pure function of (seed, round, global index i).

@@ -23,13 +23,15 @@ class FLConfig:
     rounds: int = 10
     iid: bool = True
     seed: int = 10
-    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped | secagg
+    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped | centered_clip | secagg
     trim: float = 0.1
     krum_f: int = 1
     clip_norm: float | None = None  # clipped / secagg: L2 bound C on every client update (default: 1.0 / none)
     noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
     agg_weighting: str = "samples"  # clipped: samples (n_k / n) | uniform (1 / K)
     dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
+    cc_tau: float = 1.0            # centered_clip: the clipping radius around the carried aggregate
+    cc_iters: int = 3              # centered_clip: clipping iterations per round
     secagg_bits: int = 20          # secagg: fractional bits of the fixed-point uploads, 8..30
     secagg_min_survivors: int = 2  # secagg: a round with fewer reporting clients is aborted
     prox_mu: float = 0.0           # FedProx: mu of the proximal term mu/2 |w - w_global|^2 (0 = off)
@@ -42,7 +44,10 @@ class FLConfig:
     compress_ratio: float = 0.1    # topk: fraction of the coordinates every client sends
     compress_bits: int = 4         # quant: bits per coordinate, 2..8
     error_feedback: bool = True    # keep what the codec dropped per client and add it back next round
-    attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider
+    attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider | alie | ipm
+    attack_z: float | None = None  # alie: z of mu - z * sigma (default: z_max of the round's n and f)
+    attack_eps: float = 0.5        # ipm: eps of -eps * mu
+    attack_knowledge: str = "benign"  # alie / ipm: statistics over the benign rows | the colluders' own
     malicious: int = 0             # number of malicious clients (ids 0..malicious-1)
     dropout: float = 0.0
     stragglers: float = 0.0        # probability a sampled client is slow
@@ -65,7 +70,12 @@ def build_server(cfg: FLConfig, ctx):
     parts = split(cfg.clients, cfg.iid, cfg.seed, labels=train.labels)
     model_fn = {"mnist_cnn": mnist_cnn, "mnist_mlp": mnist_mlp, "resnet18": resnet18_cifar,
                 "resnet50": resnet50_imagenet}[cfg.model]
-    attack = make_attack(cfg.attack, list(range(cfg.malicious))) if cfg.attack else None
+    akw = {}  # keyword arguments only for the colluding attacks
+    if cfg.attack == "alie":
+        akw = {"z": cfg.attack_z, "knowledge": cfg.attack_knowledge}
+    elif cfg.attack == "ipm":
+        akw = {"eps": cfg.attack_eps, "knowledge": cfg.attack_knowledge}
+    attack = make_attack(cfg.attack, list(range(cfg.malicious)), **akw) if cfg.attack else None
     algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight,
             "scaffold": Scaffold}[cfg.algorithm]
     secure = cfg.aggregator.lower() in ("secagg", "secure", "secure_mean")
@@ -76,7 +86,8 @@ def build_server(cfg: FLConfig, ctx):
               agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": clip, "frac_bits": cfg.secagg_bits,
                           "min_survivors": cfg.secagg_min_survivors,
                           "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
-                          "weighting": cfg.agg_weighting}, attack=attack, ctx=ctx,
+                          "weighting": cfg.agg_weighting, "tau": cfg.cc_tau, "iters": cfg.cc_iters},
+              attack=attack, ctx=ctx,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
               straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline, prox_mu=cfg.prox_mu)
     if cfg.server_opt:

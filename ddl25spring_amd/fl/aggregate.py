@@ -20,6 +20,9 @@
 * ``ClippedMean`` — norm bounding (Sun et al. 2019) and DP-FedAvg (McMahan et al. 2018)
   [north-star]: each update clipped to L2 norm C, then the weighted mean, optionally plus Gaussian
   noise; streaming kernels (clip_agg.hip), the mean's cross-rank route, any number of clients.
+* ``CenteredClip`` — centered clipping (Karimireddy et al. 2021) [north-star]: iterated clipping
+  around a carried estimate of the aggregate update; the clipped mean's ops, or one fused step kernel
+  per iteration on a single GPU.
 * ``SecureMean`` — secure aggregation (Bonawitz et al. 2017) [north-star]: the clipped mean on
   fixed-point uploads under pairwise masks that cancel in the sum, with recovery from dropped clients
   (secagg.hip). Key agreement and secret sharing are simulated: every mask is a pure function of
@@ -184,6 +187,97 @@ class ClippedMean(MeanAggregator):
 
     def load_state_dict(self, sd: dict) -> None:
         self.rounds, self.last_k = int(sd["rounds"]), int(sd.get("last_k", 0))
+
+
+class CenteredClip(ClippedMean):
+    """Centered clipping (Karimireddy, He, Jaggi, ICML 2021) [north-star]: ``iters`` rounds of
+    clipping *around a carried estimate of the aggregate update* ``v [P]`` (the last round's, zero
+    at the start and each round with ``warm_start=False``), not around the server model:
+
+        v^0 = v;   ctr^l = fl32(c + v^l)   (v^l itself without a centre)
+        v^{l+1} = v^l + sum_k cs_k^l * fl32(x_k - ctr^l),   cs_k^l = w_k * min(1, tau / ||x_k - ctr^l||)
+        out = ctr^L;   v <- v^L
+
+    ``w_k`` as ``ClippedMean``'s ``weighting``; a row with a non-finite norm has cs = 0 for the whole
+    round; ``last_norms`` are the first iteration's. No noise option.
+
+    Two routes (``fuse``). Unfused, for any G, several ranks and the CPU, on the clipped mean's ops:
+    per iteration update_sqnorm(rows, ctr) -> clip_scales -> clipped_sum into delta -> the mean's
+    cross-rank route -> v += delta, ctr = c + v: (2G + 9) floats per coordinate. Fused, on one GPU
+    with at most ``Fn.CC_MAX_ROWS`` rows: one norm pass, then one ``Fn.cc_step`` per iteration, which
+    forms v and ctr and the next iteration's norms in a single read of the rows:
+    (G + 1) + L (G + 5) floats. The routes fold the norm partials over different block partitions
+    and add v at different points of the sum, so they agree to rounding, not bit for bit."""
+    name = "centered_clip"
+    fuse = True  # the fused step where it applies; off for A/B runs and tests
+
+    def __init__(self, tau: float = 1.0, iters: int = 3, weighting: str = "samples",
+                 warm_start: bool = True, ordered: bool | None = None):
+        super().__init__(tau, 0.0, 0, weighting, ordered)
+        self.tau, self.iters, self.warm_start = self.clip, int(iters), bool(warm_start)
+        if self.iters < 0:
+            raise ValueError(f"iters must be >= 0, got {iters}")
+        self.v = None  # [P] on the device of the last call
+
+    def _state(self, P, dev):
+        if self.v is None or self.v.numel() != P:
+            self.v = torch.zeros(P, dtype=torch.float32, device=dev)
+        elif self.v.device != dev:
+            self.v = self.v.to(dev)
+        if not self.warm_start:
+            self.v.zero_()
+        return self.v
+
+    def _clipped(self, ctx, rows, coeffs, out, center, K_r: int):
+        G, P = rows.shape
+        dev = out.device
+        v = self._state(P, dev)
+        self._norms = None
+        if G:
+            if rows.stride(1) != 1:
+                rows = rows.contiguous()
+            if self.weighting == "uniform":
+                coeffs = self._tables.get(("uniform", G, K_r, dev),
+                                          lambda: torch.full((G,), 1.0 / K_r, dtype=torch.float32, device=dev))
+        ctr = v
+        if center is not None:  # ctr^0 = c + v^0; the last ctr goes to out, which may be the centre
+            ctr = self._tables.get(("ctr", P, dev), lambda: torch.empty(P, dtype=torch.float32, device=dev))
+            Fn.apply_update(ctr, center, v)
+        if self.fuse and not ctx.is_distributed and rows.is_cuda and 1 <= G <= Fn.CC_MAX_ROWS:
+            sq = Fn.update_sqnorm(rows, ctr) if self.iters else None
+            for l in range(self.iters):
+                last = l == self.iters - 1
+                norms, cs = Fn.clip_scales(sq, coeffs, self.tau)
+                if l == 0:
+                    self._norms = norms
+                sq = Fn.cc_step(rows, center, ctr, v, cs, v, out if last and center is not None else ctr,
+                                want_norms=not last)
+        else:
+            delta = self._tables.get(("delta", P, dev), lambda: torch.empty(P, dtype=torch.float32, device=dev))
+            for l in range(self.iters):
+                cs = None
+                if G:
+                    norms, cs = Fn.clip_scales(Fn.update_sqnorm(rows, ctr), coeffs, self.tau)
+                    if l == 0:
+                        self._norms = norms
+                self._reduce(ctx, rows, ctr, cs, delta)
+                v.add_(delta)
+                if center is not None:
+                    Fn.apply_update(out if l == self.iters - 1 else ctr, center, v)
+        if center is None or self.iters == 0:
+            out.copy_(ctr)
+        self.rounds += 1
+        self.last_k = K_r
+        return out
+
+    def state_dict(self) -> dict:
+        return {"rounds": self.rounds, "last_k": self.last_k,
+                "v":None if self.v is None else self.v.detach().cpu().clone()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        super().load_state_dict(sd)
+        v = sd.get("v")
+        self.v = None if v is None else v.detach().clone().float()
 
 
 class SecureMean(ClippedMean):
@@ -456,6 +550,9 @@ def make_aggregator(name: str, **kw):
     if name in ("clipped", "clipped_mean", "norm_clip"):
         return ClippedMean(kw.get("clip", 1.0), kw.get("noise_multiplier", 0.0), kw.get("seed", 0),
                            kw.get("weighting", "samples"))
+    if name in ("centered_clip", "cc"):
+        return CenteredClip(kw.get("tau", 1.0), kw.get("iters", 3), kw.get("weighting", "samples"),
+                            kw.get("warm_start", True))
     if name in ("secagg", "secure", "secure_mean"):
         return SecureMean(kw.get("frac_bits", 20), kw.get("clip", math.inf), kw.get("min_survivors", 2),
                           kw.get("noise_multiplier", 0.0), kw.get("seed", 0), kw.get("weighting", "samples"))

@@ -253,6 +253,18 @@ class FederatedBase:
             agg.abort_round()
         return True
 
+    def _poison(self, rows, center, chosen, mine):
+        """The model-poisoning attack on this rank's rows. An attack with ``begin_round`` is told the
+        round first; a ``collective`` one (it gathers rows over the ranks) is called on every rank
+        of a distributed run, also on one without a client."""
+        atk = self.attack
+        if atk is None:
+            return
+        if hasattr(atk, "begin_round"):
+            atk.begin_round(self.ctx, chosen, mine)
+        if len(mine) or (getattr(atk, "collective", False) and self.ctx.is_distributed):
+            atk.poison_updates(rows, center, mine)
+
     def _download(self, G):
         st = self.net.store
         if G:
@@ -389,8 +401,7 @@ class FedAvg(FederatedBase):
                 samples -= sum(self.E * self.counts[c] for c in mine if self.attack.skip_training(c))
         self._after_local(mine, chosen)
         st = self.net.store
-        if self.attack is not None and G:
-            self.attack.poison_updates(st.data[:G], self.w_global, mine)
+        self._poison(st.data[:G], self.w_global, chosen, mine)
         coeffs = self._coeffs(mine, total)
         with self.timer("aggregate"):
             self._aggregate(st.data[:G], coeffs, counts)
@@ -549,7 +560,7 @@ class FedSGD(FederatedBase):
         began = self._begin_round()
         if began is None:
             return self.ctx.max_scalar(time.perf_counter() - t0), 0
-        _, mine, counts, total = began
+        chosen, mine, counts, total = began
         G = len(mine)
         self._download(G)
         st, net = self.net.store, self.net
@@ -572,9 +583,9 @@ class FedSGD(FederatedBase):
                             y = lt(y, g0, g1)
                         net.train_step(x, y, scale=1.0 / n)
                         samples += (g1 - g0) * (e - s)
-        if self.attack is not None and G:
-            # model-poisoning attacks act on the reported gradient ("update" = -grad direction)
-            self.attack.poison_updates(st.grad[:G], torch.zeros_like(self.w_global), mine)
+        # model-poisoning attacks act on the reported gradient ("update" = -grad direction)
+        self._poison(st.grad[:G], torch.zeros_like(self.w_global) if self.attack is not None else None,
+                     chosen, mine)
         coeffs = self._coeffs(mine, total)
         aggregate_into(self.aggregator, self.ctx, st.grad[:G], coeffs, self.g_global, center=None,  # the updates
                        counts=counts, keys=self._row_keys(counts))                                  # are the gradients

@@ -6,10 +6,18 @@ reference README.md:89-92 / lab/README.md:13-16, has no code].
                       w_k <- w_g - s * (w_k - w_g).
 * ``GaussianNoise`` — the malicious update is replaced by N(0, sigma^2) noise.
 * ``FreeRider``     — sends back the server weights unchanged (no local work).
+* ``ALIE`` / ``IPM`` — colluding model poisoning: every attacker sends the same vector, built from
+                      the per-coordinate mean and std of other clients' updates (collude.hip).
 """
 from __future__ import annotations
 
+import math
+from statistics import NormalDist
+
 import torch
+
+from ..ops import functional as Fn
+from ..runtime.staging import DeviceTables
 
 
 class Attack:
@@ -131,8 +139,110 @@ class FreeRider(Attack):
                 rows[i].copy_(w_global)
 
 
+class Colluding(Attack):
+    """The colluders of a round all send ``center + p``, p a function of the per-coordinate mean and
+    population std of the *source* updates u_k = fl32(x_k - center) (``Fn.collude_rows``: one
+    streaming pass, moments in double, NaN / Inf entries skipped).
+
+    ``knowledge`` names the sources: "benign" (omniscient, the default) the reporting clients that
+    are not malicious; "own" (Baruch et al.'s setting) the reporting colluders' own honestly trained
+    rows, which exist because every slot trains. No colluder reporting: nothing is done; no source
+    row: the colluders send the centre.
+
+    The engine announces each round with ``begin_round``; without it ``poison_updates`` takes the
+    rows it is given as the whole round (one process). On several ranks the attack is *collective*:
+    every rank calls it, also one without a client; the rows are all-gathered as a [slots, P] send
+    buffer and visited in the order of the round's ``chosen`` list (position j lives at rank j % W,
+    slot j // W), so every rank computes identical statistics and the malicious rows have the same
+    bits however the clients are placed. Deterministic: no state, no host synchronisation."""
+    collective = True
+    mode = None  # "alie" | "ipm"
+
+    def __init__(self, malicious, knowledge: str = "benign"):
+        super().__init__(malicious)
+        if knowledge not in ("benign", "own"):
+            raise ValueError(f"knowledge must be 'benign' or 'own', got {knowledge!r}")
+        self.knowledge = knowledge
+        self._round = None
+        self._tables = DeviceTables()
+
+    def begin_round(self, ctx, chosen, mine) -> None:
+        """The round's reporting clients of all ranks in sampling order, and this rank's in slot order."""
+        self._round = (ctx, [int(c) for c in chosen], [int(c) for c in mine])
+
+    def coef(self, n: int, f: int) -> float:
+        """The mode's coefficient for n reporting clients, f of them colluders."""
+        raise NotImplementedError
+
+    def _table(self, ids, n_rows, dev):
+        return self._tables.get((tuple(ids), n_rows, dev), lambda: Fn.collude_table(ids, n_rows, dev))
+
+    def poison_updates(self, rows, w_global, slot_clients):
+        ctx, chosen, mine = self._round or (None, [int(c) for c in slot_clients], [int(c) for c in slot_clients])
+        self._round = None
+        if mine != [int(c) for c in slot_clients]:
+            raise ValueError("colluding attack: the rows are not those of the clients announced for the round")
+        n, f = len(chosen), sum(c in self.malicious for c in chosen)
+        if f == 0:
+            return  # the same decision on every rank: chosen is
+        is_src = (lambda c: c not in self.malicious) if self.knowledge == "benign" else (lambda c: c in self.malicious)
+        W = ctx.world if ctx is not None and ctx.is_distributed else 1
+        dev = rows.device
+        src = rows
+        if W > 1:
+            # every rank's rows, as replicate_rows (fl/bank.py) moves them: one collective, also
+            # on a rank without a client
+            slots, P = math.ceil(n / W), rows.shape[1]
+            send = torch.zeros(slots, P, dtype=torch.float32, device=dev)
+            if len(mine):
+                send[:len(mine)] = rows
+            src = ctx.all_gather_rows(send).view(W * slots, P)
+            where = lambda j: (j % W) * slots + j // W
+        else:
+            where = lambda j: j
+        src_rows = [where(j) for j, c in enumerate(chosen) if is_src(c)]
+        dst_rows = [g for g, c in enumerate(mine) if c in self.malicious]
+        if not dst_rows:
+            return
+        Fn.collude_rows(src, self._table(src_rows, src.shape[0], dev), w_global, rows,
+                        self._table(dst_rows, rows.shape[0], dev), self.mode, self.coef(n, f))
+
+
+def alie_z_max(n: int, f: int) -> float:
+    """The largest z for which ALIE's ``mu - z * sigma`` still finds enough benign support (Baruch et
+    al. 2019): z_max = Phi^-1((n - s) / n), s = floor(n / 2 + 1) - f clamped to at least 1."""
+    s = max(1, n // 2 + 1 - f)
+    q = (n - s) / n
+    return NormalDist().inv_cdf(q) if 0.0 < q < 1.0 else 0.0
+
+
+class ALIE(Colluding):
+    """"A Little Is Enough" (Baruch et al. 2019): p = mu - z * sigma per coordinate, inside the
+    spread a robust rule tolerates. ``z`` None: ``alie_z_max`` of the round's n and f."""
+    mode = "alie"
+
+    def __init__(self, malicious, z: float | None = None, knowledge: str = "benign"):
+        super().__init__(malicious, knowledge)
+        self.z = None if z is None else float(z)
+
+    def coef(self, n, f):
+        return alie_z_max(n, f) if self.z is None else self.z
+
+
+class IPM(Colluding):
+    """Inner-product manipulation (Xie et al. 2019): p = -eps * mu."""
+    mode = "ipm"
+
+    def __init__(self, malicious, eps: float = 0.5, knowledge: str = "benign"):
+        super().__init__(malicious, knowledge)
+        self.eps = float(eps)
+
+    def coef(self, n, f):
+        return self.eps
+
+
 def make_attack(name: str | None, malicious, **kw):
     if not name or name == "none":
         return None
     return {"label_flip": LabelFlip, "sign_flip": SignFlip, "gaussian": GaussianNoise,
-            "free_rider": FreeRider}[name](malicious, **kw)
+            "free_rider": FreeRider, "alie": ALIE, "ipm": IPM}[name](malicious, **kw)

@@ -186,6 +186,10 @@ _SIGS = {
     "ddl_clip_scales": [vp, vp, i32, f64, vp, vp, vp],
     "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
     "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
+    "ddl_cc_step_blocks": [i64],
+    "ddl_cc_step": [vp, i64, vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, vp],
+    # collude.hip
+    "ddl_collude": [vp, i64, vp, i32, vp, vp, i64, vp, i32, i64, i32, f64, vp],
     # fedopt.hip
     "ddl_sgd_corrected": [ctypes.POINTER(SGDCorrectedArgs), vp],
     "ddl_server_opt": [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],

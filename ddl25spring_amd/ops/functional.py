@@ -1933,3 +1933,90 @@ def apply_update(out, center, delta, std: float = 0.0, seed: int = 0, round: int
         check(_lib.kernels().ddl_apply_update(ptr(out), ptr(center), ptr(delta), n, offset, std, seed, round,
                                               stream()), "apply_update")
     return out
+
+
+CC_MAX_ROWS = 16  # rows the fused centered-clipping step holds in registers (clip_agg.hip)
+
+
+def cc_step(rows, center, ctr_in, v_in, cs, v_out, ctr_out, want_norms: bool = True):
+    """One centered-clipping iteration in one read of the rows (clip_agg.hip, ``ddl_cc_step``):
+
+        v_out   = v_in + sum_k cs[k] * fl32(rows[k] - ctr_in)   (``clipped_sum``'s order and roundings,
+                                                                 rows with cs[k] == 0 not read)
+        ctr_out = center + v_out                                 (v_out without a centre)
+
+    and with ``want_norms`` -> sq [G] float64, the next iteration's squared norms
+    sum_i fl32(rows[k, i] - ctr_out[i])^2 (+inf for a row that was not read), else None.
+    ``v_out`` may be ``v_in``; ``ctr_out`` may be ``ctr_in`` or ``center``. On the device: at most
+    ``CC_MAX_ROWS`` rows of unit inner stride."""
+    if not rows.is_cuda:
+        return ref.cc_step(rows, center, ctr_in, v_in, cs, v_out, ctr_out, want_norms)
+    G, n = rows.shape
+    if not 1 <= G <= CC_MAX_ROWS:
+        raise ValueError(f"cc_step: 1..{CC_MAX_ROWS} rows, got {G}")
+    assert rows.dtype == torch.float32 and rows.stride(1) == 1
+    for t in (ctr_in, v_in, v_out, ctr_out) + (() if center is None else (center,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == rows.device
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == G
+    if n == 0:
+        return torch.zeros(G, dtype=torch.float64, device=rows.device) if want_norms else None
+    sq = part = None
+    cap = 0
+    if want_norms:
+        cap = G * _lib.kernels().ddl_cc_step_blocks(n)
+        part = torch.empty(cap, dtype=torch.float64, device=rows.device)
+        sq = torch.empty(G, dtype=torch.float64, device=rows.device)
+        sq._keep = part  # the scratch must outlive the (asynchronous) launches
+    check(_lib.kernels().ddl_cc_step(ptr(rows), rows.stride(0), ptr(center), ptr(ctr_in), ptr(v_in), ptr(cs), G, n,
+                                     ptr(v_out), ptr(ctr_out), ptr(part), cap, ptr(sq), stream()), "cc_step")
+    return sq
+
+
+# ---------------------------------------------------------------- colluding attacks (collude.hip)
+COLLUDE_MODES = {"alie": 0, "ipm": 1}
+
+
+def collude_table(ids, n_rows: int, device, what: str = "rows"):
+    """The host-side check of a row table before it goes to the device: every id a row of the buffer
+    (0 <= id < n_rows). The kernel takes the table as it is. -> int32 device tensor."""
+    ids = [int(i) for i in ids]
+    if any(i < 0 or i >= n_rows for i in ids):
+        raise ValueError(f"collude_rows: {what} must lie in [0, {n_rows}), got {ids}")
+    return torch.tensor(ids, dtype=torch.int32, device=device)
+
+
+def collude_rows(src, src_rows, center, dst, dst_rows, mode, coef: float):
+    """The colluders' common vector from per-coordinate statistics of the source rows, written to
+    every destination row (collude.hip). Per coordinate i, over the rows ``src[src_rows[j]]`` in
+    table order with d = fl32(src - center) finite (m_i of them; none: p_i = 0):
+
+        mu, sigma = mean and population std of d, in double, one pass on values shifted by the
+                    coordinate's first finite d
+        "alie": p = fl32(mu - coef * sigma)        "ipm": p = fl32(-coef * mu)
+        dst[dst_rows[t], i] = center[i] + p        (p without a centre)
+
+    ``src_rows`` / ``dst_rows``: host lists (checked against the buffers here), or int32 device
+    tables built by ``collude_table``. ``dst`` may be ``src`` and ``dst_rows`` may name source rows."""
+    mode = COLLUDE_MODES[mode] if isinstance(mode, str) else int(mode)
+    if mode not in (0, 1):
+        raise ValueError(f"collude_rows: mode must be 0 (alie) or 1 (ipm), got {mode}")
+    coef = float(coef)
+    if not torch.is_tensor(src_rows):
+        src_rows = collude_table(src_rows, src.shape[0], src.device, "src_rows")
+    if not torch.is_tensor(dst_rows):
+        dst_rows = collude_table(dst_rows, dst.shape[0], dst.device, "dst_rows")
+    n = dst.shape[1]
+    ns, nd = src_rows.numel(), dst_rows.numel()
+    assert src.shape[1] == n and src_rows.dtype == torch.int32 and dst_rows.dtype == torch.int32
+    if nd == 0 or n == 0:
+        return dst
+    if not dst.is_cuda:
+        ref.collude_rows(src, src_rows, center, dst, dst_rows, mode, coef)
+        return dst
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.device == dst.device
+    assert (src.shape[0] == 0 or src.stride(1) == 1) and dst.stride(1) == 1
+    assert center is None or (center.dtype == torch.float32 and center.is_contiguous() and center.numel() == n)
+    assert src_rows.is_contiguous() and dst_rows.is_contiguous() and src_rows.device == dst.device
+    check(_lib.kernels().ddl_collude(ptr(src), src.stride(0), ptr(src_rows), ns, ptr(center), ptr(dst), dst.stride(0),
+                                     ptr(dst_rows), nd, n, mode, coef, stream()), "collude_rows")
+    return dst

@@ -405,6 +405,49 @@ def clipped_sum(rows, center, cs, out, accumulate=False):
     out.copy_(acc)
 
 
+def cc_step(rows, center, ctr_in, v_in, cs, v_out, ctr_out, want_norms=True):
+    """cc_step_kernel's twin: the sum starts from v_in and adds the rows in order."""
+    acc = v_in.clone()
+    live = [k for k, c in enumerate(cs.tolist()) if c != 0.0]
+    for k in live:
+        acc = acc + cs[k] * (rows[k] - ctr_in)
+    ctr = acc if center is None else center + acc
+    v_out.copy_(acc)
+    ctr_out.copy_(ctr)
+    if not want_norms:
+        return None
+    sq = torch.full((rows.shape[0],), float("inf"), dtype=torch.float64)
+    for k in live:
+        sq[k] = (rows[k] - ctr).double().square().sum()
+    return sq
+
+
+# ------------------------------------------------- colluding attacks (collude.hip), float64 twin
+def collude_rows(src, src_rows, center, dst, dst_rows, mode, coef):
+    """collude_kernel's definition in torch float64: one pass over the source rows in table order,
+    moments of the finite d = fl32(src - center) shifted by each coordinate's first finite d."""
+    n = dst.shape[1]
+    shift = torch.zeros(n, dtype=torch.float64)
+    s1, s2, m = torch.zeros_like(shift), torch.zeros_like(shift), torch.zeros_like(shift)
+    for j in src_rows.tolist():
+        d = src[j] if center is None else src[j] - center  # rounded to fp32
+        ok = torch.isfinite(d)
+        d = torch.where(ok, d, torch.zeros_like(d)).double()
+        shift = torch.where(ok & (m == 0), d, shift)
+        t = torch.where(ok, d - shift, torch.zeros_like(d))
+        s1, s2, m = s1 + t, s2 + t * t, m + ok.double()
+    cnt = m.clamp_min(1.0)
+    mu = shift + s1 / cnt
+    if mode == 0:
+        p = mu - coef * ((s2 - s1 * s1 / cnt) / cnt).clamp_min(0.0).sqrt()
+    else:
+        p = -coef * mu
+    p = torch.where(m > 0, p, torch.zeros_like(p)).float()
+    row = p if center is None else center + p
+    for t in dst_rows.tolist():
+        dst[t].copy_(row)
+
+
 # ------------------------------------------------ FedProx / FedOpt (fedopt.hip), fp32 torch twins
 def _s32(x):
     return torch.tensor(float(x), dtype=torch.float32)
