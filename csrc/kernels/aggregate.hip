@@ -12,6 +12,9 @@
 //                        [north-star, absent in reference].
 //   ddl_coord_select   : coordinate-wise median / trimmed mean over K <= 128 client vectors by an
 //                        in-register bitonic sort per coordinate (Yin et al. 2018) [north-star].
+//   ddl_bulyan_select / ddl_bulyan_coord : Bulyan (El Mhamdi et al. 2018) [north-star]: iterated Krum
+//                        selection on the Gram, then per coordinate the mean of the selected values
+//                        nearest their median (see there).
 #include "quad_stream.h"
 
 __global__ void weighted_sum_kernel(const float* __restrict__ src, long long ld,
@@ -422,4 +425,174 @@ DDL_API int ddl_mean_rows_idx(const float* X, long long ld, const int* sel, int 
   if (m < 1 || n < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(mean_rows_idx_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, X, ld, sel, m, n, out);
   return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bulyan (El Mhamdi, Guerraoui, Rouault 2018): theta = K - 2f rounds of Krum on the clients not yet
+// picked, then per coordinate the mean of the beta = theta - 2f picked values nearest their median.
+//
+// Selection, from the K x K Gram, one block, a thread per client as krum_select_kernel and with its
+// distances and its rules for non-finite values. Round t, n' = K - t clients left (R): nb_t =
+// min(max(n' - f - 2, 1), n' - 1); score_i = the nb_t smallest d2[i][j], j in R \ {i}, added in
+// ascending order; the least (score, key) goes to sel[t] and leaves R. The row is sorted once, in
+// registers; when client w leaves, every thread takes one value equal to d2[i][w] (the same
+// expression, so the same bits) out of its sorted row -- static moves behind the first match, +inf
+// shifted in at the end -- which leaves the sorted distances to R \ {i}, as a fresh sort would (there
+// are n' - 1 >= nb_t of them before the +inf of the padding, of i itself and of the clients that
+// left). R is a 128-bit mask held by every thread (uniform); a round costs two barriers.
+__device__ __forceinline__ float krum_dist(float gii, float gjj, float gij) {
+#pragma clang fp contract(off)
+  const float x = gii + gjj - 2.f * gij;
+  return (fabsf(x) < INFINITY) ? fmaxf(x, 0.f) : INFINITY;
+}
+
+template <int KP>
+__global__ __launch_bounds__(128) void bulyan_select_kernel(const float* __restrict__ gram, int K, int f,
+                                                            const int* __restrict__ keys,
+                                                            float* __restrict__ win, int* __restrict__ sel) {
+  __shared__ float sc[128];
+  __shared__ float diag[128];
+  __shared__ int key[128];
+  const int i = threadIdx.x;
+  if (i < K) {
+    diag[i] = gram[i * K + i];
+    key[i] = keys ? keys[i] : i;
+  }
+  __syncthreads();
+  unsigned long long r0 = ~0ull, r1 = ~0ull;  // R: bit j of (r0, r1) set while client j is in it
+  const int theta = K - 2 * f;
+  const float gii = i < K ? diag[i] : 0.f;
+  const float* row = gram + (i < K ? i : 0) * K;
+  float v[KP];
+#pragma unroll
+  for (int j = 0; j < KP; ++j) v[j] = (j < K && j != i && i < K) ? krum_dist(gii, diag[j], row[j]) : INFINITY;
+  sort_values<KP>(v);
+  for (int t = 0; t < theta; ++t) {
+    const int left = K - t;
+    int nb = left - f - 2;
+    nb = nb < 1 ? 1 : nb;
+    nb = nb > left - 1 ? left - 1 : nb;
+    if (i < K) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < KP; ++j)
+        if (j < nb) s += v[j];
+      sc[i] = s;
+    }
+    __syncthreads();
+    // every thread finds the same winner: scores are in [0, +inf], never NaN
+    int w = -1, wk = 0;
+    float ws = 0.f;
+    for (int j = 0; j < K; ++j) {
+      const bool in = ((j < 64 ? r0 >> j : r1 >> (j - 64)) & 1ull) != 0;
+      if (!in) continue;
+      const float s = sc[j];
+      const int kj = key[j];
+      if (w < 0 || s < ws || (s == ws && kj < wk)) { w = j; ws = s; wk = kj; }
+    }
+    if (i == 0) {
+      sel[t] = w;
+      if (win) win[t] = ws;
+    }
+    if (w < 64) r0 &= ~(1ull << w); else r1 &= ~(1ull << (w - 64));
+    // the winner's own row is not read again; everyone else drops its distance to the winner
+    const float d = (i < K && i != w) ? krum_dist(gii, diag[w], row[w]) : INFINITY;
+    bool past = false;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      past = past || (v[j] == d);
+      v[j] = past ? (j + 1 < KP ? v[j + 1] : INFINITY) : v[j];
+    }
+    __syncthreads();  // sc is rewritten by the next round
+  }
+}
+
+DDL_API int ddl_bulyan_select(const float* gram, int K, int f, const int* keys, float* win, int* sel,
+                              hipStream_t st) {
+  if (K < 1 || K > 128 || f < 0 || f > 31 || K < 4 * f + 3) return (int)hipErrorInvalidValue;  // f > 31 first: 4f + 3 cannot wrap
+#define BULYAN_SEL_CASE(KP_) \
+  if (K <= KP_) { \
+    hipLaunchKernelGGL(bulyan_select_kernel<KP_>, dim3(1), dim3(128), 0, st, gram, K, f, keys, win, sel); \
+    return (int)hipGetLastError(); \
+  }
+  BULYAN_SEL_CASE(8) BULYAN_SEL_CASE(16) BULYAN_SEL_CASE(32) BULYAN_SEL_CASE(64) BULYAN_SEL_CASE(128)
+#undef BULYAN_SEL_CASE
+  return (int)hipErrorInvalidValue;
+}
+
+// Bulyan's coordinate step over the theta rows X[sel[t]] (read by index, as mean_rows_idx_kernel;
+// an index outside [0, K) is not read and counts as +inf): one coordinate per thread, the values
+// sorted ascending to s[0 .. theta) with a NaN as +inf, as coord_select_kernel. With a = (theta-1)/2,
+// b = theta/2, the kept window is [lo, lo + beta),
+//   lo = #{ i in [0, theta - beta) : (double)s[i] + (double)s[i+beta] < (double)s[a] + (double)s[b] },
+// the beta values nearest the median, an exact tie going to the lower value: window i+1 beats window
+// i exactly when s[i+beta] is nearer the median than s[i], and s[i] + s[i+beta] is nondecreasing
+// in i, so the true indices are a prefix. The sums are exact in double, so a float64 oracle
+// decides alike (a wrong decision moves the result by |s[i+beta] - s[i]| / beta, beyond any
+// rounding bound). out = the fp32 sum of the window in ascending order / beta.
+// s[i + beta] for the runtime beta: a barrel shifter over the bits of beta, each stage a set of
+// static register moves under a uniform branch -- a dynamic index would send s to scratch memory.
+template <int KP>
+__global__ __launch_bounds__(256) void bulyan_coord_kernel(const float* __restrict__ X, long long ld, int K,
+                                                           const int* __restrict__ sel, int theta, int beta,
+                                                           long long n, float* __restrict__ out) {
+  const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (e < n) {
+    float v[KP], sh[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) {
+      // uniform branches around each load. Measured against issuing every load unconditionally
+      // from a clamped row index and replacing the value afterwards (as coord_select_kernel walks
+      // its rows): 0.076 against 0.135 ms over 6 of 8 x 11.19M rows, so the branches stay
+      float x = INFINITY;
+      if (i < theta) {
+        const int r = sel[i];
+        if (r >= 0 && r < K) x = X[(long long)r * ld + e];
+      }
+      v[i] = (x == x) ? x : INFINITY;
+    }
+    sort_values<KP>(v);
+    const int a = (theta - 1) / 2, b = theta / 2;
+    float va = 0.f, vb = 0.f;
+#pragma unroll
+    for (int i = 0; i < KP; ++i) {
+      if (i == a) va = v[i];
+      if (i == b) vb = v[i];
+      sh[i] = v[i];
+    }
+#pragma unroll
+    for (int bit = 1; bit < KP; bit <<= 1) {
+      if (beta & bit) {  // sh[i] <- sh[i + bit], ascending i: the source is still the old value
+#pragma unroll
+        for (int i = 0; i < KP; ++i) sh[i] = (i + bit < KP) ? sh[i + bit] : INFINITY;
+      }
+    }
+    const double mid = (double)va + (double)vb;
+    const int span = theta - beta;
+    int lo = 0;
+#pragma unroll
+    for (int i = 0; i < KP; ++i)
+      if (i < span) lo += ((double)v[i] + (double)sh[i] < mid) ? 1 : 0;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < KP; ++i)
+      if (i >= lo && i < lo + beta) s += v[i];
+    out[e] = s / (float)beta;
+  }
+}
+
+DDL_API int ddl_bulyan_coord(const float* X, long long ld, int K, const int* sel, int theta, int beta,
+                             long long n, float* out, hipStream_t s) {
+  if (K < 1 || n < 1 || beta < 1 || beta > theta || theta > 128 || ((theta - beta) & 1))
+    return (int)hipErrorInvalidValue;
+  const long long blocks = (n + 255) / 256;
+  if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+#define BULYAN_CASE(KP_) \
+  if (theta <= KP_) { \
+    hipLaunchKernelGGL(bulyan_coord_kernel<KP_>, dim3(blocks), dim3(256), 0, s, X, ld, K, sel, theta, beta, n, out); \
+    return (int)hipGetLastError(); \
+  }
+  BULYAN_CASE(8) BULYAN_CASE(16) BULYAN_CASE(32) BULYAN_CASE(64) BULYAN_CASE(128)
+#undef BULYAN_CASE
+  return (int)hipErrorInvalidValue;
 }

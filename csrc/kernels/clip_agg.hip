@@ -9,6 +9,8 @@
 //   ddl_apply_update  : w[i] = c[i] + delta[i] + std * z_i, z_i ~ N(0, 1) from Philox
 //   ddl_cc_step       : one centered-clipping iteration, v += sum_k cs[k] * fl32(x_k - ctr), fused
 //                       with the next iteration's squared norms (up to 16 rows, see there)
+//   ddl_gm_scales     : the row scales of one smoothed Weiszfeld iteration (geometric median / RFA),
+//                       cs[k] = (coeff[k] / max(nu, norms[k])) / their sum; the step itself is ddl_cc_step
 //
 // All four stream: two reads of the client rows (norms, then the sum), no LDS tiling, no scratch,
 // no float atomics, and no block waits for another: the per-block partial squared norms go out with
@@ -125,6 +127,61 @@ DDL_API int ddl_clip_scales(const double* sq, const float* coeff, int G, double 
   if (G < 1 || !(clip > 0.0)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(clip_scales_kernel, dim3(grid_for(G, 256)), dim3(256), 0, s, sq, coeff, G, clip,
                      norms, cs);
+  return (int)hipGetLastError();
+}
+
+// The row scales of one smoothed Weiszfeld iteration (geometric median / RFA, Pillutla et al. 2022),
+// one block, double throughout: norms[k] = sqrt(sq_k); beta_k = coeff_k / max(nu, sqrt(sq_k)), or
+// coeff_k itself with `init` (the weighted mean as the starting point), and 0 for a row whose
+// squared norm is NaN / Inf; S = beta_0 + beta_1 + ... added by one thread in index order (the
+// betas of 256 rows at a time computed by the block into LDS), so that the ranks' partial S added
+// in rank order give the bits of one process holding the rows in that order; beta_sum[0] = S;
+// cs[k] = beta_k / T rounded to fp32, T = *total when given (the S of all ranks), else S; T == 0
+// (no row left, or all weights 0) gives cs = 0 throughout.
+__device__ __forceinline__ double gm_beta(double q, float coeff, double nu, int init) {
+  if (!(q < (double)INFINITY)) return 0.0;  // NaN and +inf
+  if (init) return (double)coeff;
+  const double nrm = sqrt(q);
+  return (double)coeff / (nrm > nu ? nrm : nu);
+}
+
+__global__ __launch_bounds__(256) void gm_scales_kernel(const double* __restrict__ sq, const float* __restrict__ coeff,
+                                                        int G, double nu, int init, const double* __restrict__ total,
+                                                        float* __restrict__ norms, float* __restrict__ cs,
+                                                        double* __restrict__ beta_sum) {
+#pragma clang fp contract(off)
+  __shared__ double chunk[256];
+  __shared__ double sum;
+  const int tid = threadIdx.x;
+  double S = 0.0;
+  for (int base = 0; base < G; base += 256) {
+    const int k = base + tid;
+    if (k < G) {
+      const double q = sq[k];
+      norms[k] = (float)sqrt(q);  // +inf for a finite row too long for fp32
+      chunk[tid] = gm_beta(q, coeff[k], nu, init);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int m = G - base < 256 ? G - base : 256;
+      for (int j = 0; j < m; ++j) S += chunk[j];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    beta_sum[0] = S;
+    sum = total ? *total : S;
+  }
+  __syncthreads();
+  const double T = sum;
+  for (int k = tid; k < G; k += 256) cs[k] = (T == 0.0) ? 0.f : (float)(gm_beta(sq[k], coeff[k], nu, init) / T);
+}
+
+DDL_API int ddl_gm_scales(const double* sq, const float* coeff, int G, double nu, int init, const double* total,
+                          float* norms, float* cs, double* beta_sum, hipStream_t s) {
+  if (G < 1 || (!init && !(nu > 0.0))) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(gm_scales_kernel, dim3(1), dim3(256), 0, s, sq, coeff, G, nu, init, total, norms, cs,
+                     beta_sum);
   return (int)hipGetLastError();
 }
 

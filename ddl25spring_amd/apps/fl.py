@@ -23,15 +23,17 @@ class FLConfig:
     rounds: int = 10
     iid: bool = True
     seed: int = 10
-    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | clipped | centered_clip | secagg
+    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | bulyan | clipped | centered_clip | geomed | secagg
     trim: float = 0.1
-    krum_f: int = 1
+    krum_f: int = 1                # krum / multi_krum / bulyan: the Byzantine clients assumed
     clip_norm: float | None = None  # clipped / secagg: L2 bound C on every client update (default: 1.0 / none)
     noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
-    agg_weighting: str = "samples"  # clipped: samples (n_k / n) | uniform (1 / K)
+    agg_weighting: str = "samples"  # clipped / centered_clip / geomed: samples (n_k / n) | uniform (1 / K)
     dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
     cc_tau: float = 1.0            # centered_clip: the clipping radius around the carried aggregate
     cc_iters: int = 3              # centered_clip: clipping iterations per round
+    gm_iters: int = 3              # geomed: smoothed Weiszfeld iterations per round
+    gm_nu: float = 1e-6            # geomed: the floor of a distance in the weights a_k / max(nu, d_k)
     secagg_bits: int = 20          # secagg: fractional bits of the fixed-point uploads, 8..30
     secagg_min_survivors: int = 2  # secagg: a round with fewer reporting clients is aborted
     prox_mu: float = 0.0           # FedProx: mu of the proximal term mu/2 |w - w_global|^2 (0 = off)
@@ -86,7 +88,8 @@ def build_server(cfg: FLConfig, ctx):
               agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": clip, "frac_bits": cfg.secagg_bits,
                           "min_survivors": cfg.secagg_min_survivors,
                           "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
-                          "weighting": cfg.agg_weighting, "tau": cfg.cc_tau, "iters": cfg.cc_iters},
+                          "weighting": cfg.agg_weighting, "tau": cfg.cc_tau, "iters": cfg.cc_iters,
+                          "gm_iters": cfg.gm_iters, "gm_nu": cfg.gm_nu},
               attack=attack, ctx=ctx,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
               straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline, prox_mu=cfg.prox_mu)

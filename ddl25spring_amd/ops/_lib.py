@@ -180,10 +180,13 @@ _SIGS = {
     "ddl_pack_shards": [vp, i64, i32, i64, i32, i64, i32, vp, vp],
     "ddl_krum_select": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ddl_mean_rows_idx": [vp, i64, vp, i32, i64, vp, vp],
+    "ddl_bulyan_select": [vp, i32, i32, vp, vp, vp, vp],
+    "ddl_bulyan_coord": [vp, i64, i32, vp, i32, i32, i64, vp, vp],
     # clip_agg.hip
     "ddl_update_sqnorm_workspace": [i32, i64],
     "ddl_update_sqnorm": [vp, i64, vp, i32, i64, vp, i64, vp, vp],
     "ddl_clip_scales": [vp, vp, i32, f64, vp, vp, vp],
+    "ddl_gm_scales": [vp, vp, i32, f64, i32, vp, vp, vp, vp, vp],
     "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
     "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
     "ddl_cc_step_blocks": [i64],

@@ -1849,6 +1849,59 @@ def coord_select(X, mode: str, trim: int = 0):
     return out
 
 
+def bulyan_select(gram, f: int, keys=None):
+    """Bulyan's selection (El Mhamdi et al. 2018) from a K x K Gram: theta = K - 2f rounds of Krum
+    on the clients not yet picked -> (win_scores [theta] fp32: the score each winner had when it was
+    picked, sel [theta] int32 row indices in order of selection).
+
+    Round t, n' = K - t clients left: nb_t = min(max(n' - f - 2, 1), n' - 1); score_i = the nb_t
+    smallest d2[i][j] over the others still left, added in ascending order; the least (score, key)
+    is picked and leaves. Distances, non-finite values and ``keys`` as ``krum_select``, so sel[0] is
+    ``krum_select(gram, K - f - 2, 1)``'s winner. Needs K >= 4f + 3."""
+    K, f = gram.shape[0], int(f)
+    _robust_k(K, "bulyan_select")
+    if f < 0 or K < 4 * f + 3:
+        raise ValueError(f"bulyan_select: K={K} client rows with f={f}; Bulyan takes K >= 4f + 3")
+    if keys is None:
+        keys = list(range(K))
+    if not gram.is_cuda:
+        win, sel = ref.bulyan_select(gram, f, keys)
+        return win, torch.tensor(sel, dtype=torch.int32)
+    assert gram.dtype == torch.float32 and gram.is_contiguous()
+    theta = K - 2 * f
+    win = torch.empty(theta, dtype=torch.float32, device=gram.device)
+    sel = torch.empty(theta, dtype=torch.int32, device=gram.device)
+    kt = torch.tensor(keys, dtype=torch.int32).to(gram.device, non_blocking=True)
+    check(_lib.kernels().ddl_bulyan_select(ptr(gram), K, f, ptr(kt), ptr(win), ptr(sel), stream()),
+          "bulyan_select")
+    win._keep = kt
+    return win, sel
+
+
+def bulyan_coord(X, sel, beta: int):
+    """Bulyan's coordinate step over the theta = len(sel) rows X[sel[t]] of X [K, n] -> out [n]: per
+    coordinate, the values sorted to s[0 .. theta) with a NaN as +inf, and the mean of the ``beta``
+    of them nearest the median (an exact tie going to the lower value), an fp32 sum in ascending
+    order. The window is [lo, lo + beta) with a = (theta-1)//2, b = theta//2 and
+
+        lo = #{ i < theta - beta : s[i] + s[i+beta] < s[a] + s[b] }   (both sums exact, in double)
+
+    ``theta - beta`` must be even (it is 2f). beta == theta is the plain mean in sorted order."""
+    theta, beta = sel.numel(), int(beta)
+    if not 1 <= beta <= theta or (theta - beta) % 2:
+        raise ValueError(f"bulyan_coord: beta={beta} of theta={theta} rows; 1 <= beta <= theta, theta - beta even")
+    _robust_k(theta, "bulyan_coord")
+    if not X.is_cuda:
+        return ref.bulyan_coord(X, sel, beta)
+    assert X.dtype == torch.float32 and X.stride(1) == 1 and sel.dtype == torch.int32 and sel.is_contiguous()
+    K, n = X.shape
+    out = torch.empty(n, dtype=torch.float32, device=X.device)
+    if n:
+        check(_lib.kernels().ddl_bulyan_coord(ptr(X), X.stride(0), K, ptr(sel), theta, beta, n, ptr(out),
+                                              stream()), "bulyan_coord")
+    return out
+
+
 # ---------------------------------------------------------------- clipped aggregation (clip_agg.hip)
 def update_sqnorm(rows, center=None):
     """sq[k] = sum_i fl32(rows[k, i] - center[i])^2 -> float64 [G]: the difference rounded to fp32
@@ -1890,6 +1943,36 @@ def clip_scales(sq, coeff, clip: float):
               "clip_scales")
         cs._keep = coeff
     return norms, cs
+
+
+def gm_scales(sq, coeff, nu: float, init: bool = False, total=None):
+    """The row scales of one smoothed Weiszfeld iteration (geometric median / RFA, clip_agg.hip
+    ``ddl_gm_scales``), in double: squared distances sq [G] (float64), weights coeff [G] ->
+    (norms [G] fp32 = sqrt(sq), cs [G] fp32, beta_sum [1] float64).
+
+        beta_k = coeff_k / max(nu, sqrt(sq_k))   (``init``: coeff_k itself, the weighted mean's scales)
+        beta_k = 0 for a row whose squared norm is NaN / Inf
+        S = beta_0 + beta_1 + ... in index order;  beta_sum[0] = S
+        cs_k = fl32(beta_k / T),  T = total[0] when given (the S of all ranks), else S;  T == 0: cs = 0
+
+    Nothing is copied to the host."""
+    nu, init = float(nu), bool(init)
+    if not init and not nu > 0.0:
+        raise ValueError(f"gm_scales: nu must be positive, got {nu}")
+    if not sq.is_cuda:
+        return ref.gm_scales(sq, coeff, nu, init, total)
+    G = sq.numel()
+    assert sq.dtype == torch.float64 and sq.is_contiguous() and coeff.numel() == G
+    assert total is None or (total.dtype == torch.float64 and total.numel() == 1 and total.device == sq.device)
+    norms = torch.empty(G, dtype=torch.float32, device=sq.device)
+    cs = torch.empty(G, dtype=torch.float32, device=sq.device)
+    beta_sum = torch.zeros(1, dtype=torch.float64, device=sq.device)
+    if G:
+        coeff = coeff.float().contiguous()
+        check(_lib.kernels().ddl_gm_scales(ptr(sq), ptr(coeff), G, nu, int(init), ptr(total), ptr(norms), ptr(cs),
+                                           ptr(beta_sum), stream()), "gm_scales")
+        cs._keep = (coeff, total)
+    return norms, cs, beta_sum
 
 
 def clipped_sum(rows, center, cs, out, accumulate=False):

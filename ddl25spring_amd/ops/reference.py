@@ -380,6 +380,46 @@ def coord_select(X, mode, trim=0):
     return s[trim:K - trim].mean(0)
 
 
+def bulyan_select(gram, f, keys):
+    """bulyan_select_kernel's twin in fp32 -> (the winners' scores [theta], sel as a list): the
+    kernel's distances, the nb_t smallest among the clients still in R added in ascending order,
+    the least (score, key) picked and removed, theta = K - 2f times."""
+    K = gram.shape[0]
+    inf = float("inf")
+    sq = torch.diagonal(gram)
+    d2 = sq[:, None] + sq[None, :] - 2 * gram
+    d2 = torch.where(torch.isfinite(d2), d2.clamp_min(0), torch.full_like(d2, inf))
+    d2.fill_diagonal_(inf)
+    left, sel, win = list(range(K)), [], []
+    for t in range(K - 2 * f):
+        n1 = K - t
+        nb = min(max(n1 - f - 2, 1), n1 - 1)
+        idx = torch.tensor(left)
+        near = torch.sort(d2[idx][:, idx], 1).values
+        score = torch.zeros(n1, dtype=gram.dtype)
+        for j in range(nb):
+            score = score + near[:, j]
+        sc = score.tolist()  # in [0, +inf], never NaN
+        w = min(range(n1), key=lambda a: (sc[a], int(keys[left[a]])))
+        sel.append(left.pop(w))
+        win.append(sc[w])
+    return torch.tensor(win, dtype=gram.dtype), sel
+
+
+def bulyan_coord(X, sel, beta):
+    """bulyan_coord_kernel's twin: the window compared in double, its fp32 sum in ascending order."""
+    s = X.index_select(0, sel.long())
+    s = torch.sort(torch.where(torch.isnan(s), torch.full_like(s, float("inf")), s), 0).values
+    theta = s.shape[0]
+    span = theta - beta
+    mid = s[(theta - 1) // 2].double() + s[theta // 2].double()
+    lo = ((s[:span].double() + s[beta:].double()) < mid).sum(0)
+    acc = torch.zeros(s.shape[1], dtype=s.dtype)
+    for j in range(beta):
+        acc = acc + s.gather(0, (lo + j)[None])[0]
+    return acc / beta
+
+
 # ------------------------------------------------- clipped aggregation (clip_agg.hip), torch twins
 def update_sqnorm(rows, center=None):
     d = rows if center is None else rows - center  # rounded to fp32, then squared in double
@@ -393,6 +433,20 @@ def clip_scales(sq, coeff, clip):
     cs = coeff.float() * s
     cs = torch.where(torch.isfinite(sq), cs, torch.zeros_like(cs))  # NaN / Inf row: skipped
     return nrm.float(), cs
+
+
+def gm_scales(sq, coeff, nu, init, total=None):
+    """gm_scales_kernel's twin, in double: -> (norms fp32, cs fp32, beta_sum float64 [1])."""
+    q = sq.double()
+    nrm = q.sqrt()
+    beta = coeff.double() if init else coeff.double() / nrm.clamp_min(nu)
+    beta = torch.where(q < float("inf"), beta, torch.zeros_like(beta))  # NaN / Inf row: weight 0
+    S = 0.0
+    for b in beta.tolist():  # index order
+        S += b
+    T = S if total is None else float(total)
+    cs = torch.zeros_like(beta) if T == 0.0 else beta / T
+    return nrm.float(), cs.float(), torch.tensor([S], dtype=torch.float64)
 
 
 def clipped_sum(rows, center, cs, out, accumulate=False):
