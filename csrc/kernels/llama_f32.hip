@@ -1020,6 +1020,189 @@ DDL_API int ddl_cevf(const float* z, const int* labels, int R, int V, long long 
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Vocabulary-PARALLEL cross-entropy: rank t holds the logit columns [v0, v0 + Vl) of every row,
+// z [R][Vl] (row stride ld). No rank sees a full row, so the loss is made in two launches around an
+// all-gather: ddl_cevp_stats reads the shard once and leaves one record per row,
+//   stats[r] = { local max (log2 domain), local sum of exp2, target logit if it is in the shard, 0 },
+// the W ranks' records are gathered to [W][R][4], and ddl_cevp_grad merges them in rank order (the
+// (m, s) merge of block_maxsum, so every rank forms the same lse bits), writes rowloss / the loss
+// and, when asked, d = (softmax - onehot) * (*inv) from a second read of the shard.
+constexpr int CEVP_REC = 4;
+
+// a logit in the log2 domain, rounded once and never contracted into the subtraction that follows:
+// x - m must be the same bits in the statistics and in the gradient pass (0 for the maximum itself)
+__device__ __forceinline__ float cevp_x(float z) { return __fmul_rn(z, LOG2E); }
+
+__device__ __forceinline__ void cevp_write_stats(float m, float s, const float* zr, int lab, int v0, int Vl,
+                                                 int ignore_index, float* rec) {
+  if (threadIdx.x != 0) return;
+  const int c = lab - v0;  // ignored / negative labels never index the shard
+  const bool mine = lab != ignore_index && lab >= v0 && c < Vl;
+  rec[0] = m;
+  rec[1] = s;
+  rec[2] = mine ? zr[c] : 0.f;
+  rec[3] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void cevp_stats_kernel(const float* __restrict__ z, const int* __restrict__ labels,
+                                                         int Vl, long long ld, int v0, int ignore_index, bool vec,
+                                                         float* __restrict__ stats) {
+  __shared__ float sm[8];
+  const int row = blockIdx.x;
+  const float* zr = z + row * ld;
+  float m = -INFINITY, s = 0.f;
+  // cevf_rows_kernel's running (m, s); an all -inf prefix keeps s = 0 (exp2f(-inf - -inf) is NaN)
+  if (vec) {
+    for (int c = threadIdx.x; c < Vl / 4; c += 256) {
+      const float4 v = ((const float4*)zr)[c];
+      const float x[4] = {cevp_x(v.x), cevp_x(v.y), cevp_x(v.z), cevp_x(v.w)};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float nm = fmaxf(m, x[k]);
+        if (nm != -INFINITY) s = s * exp2f(m - nm) + exp2f(x[k] - nm);
+        m = nm;
+      }
+    }
+  } else {
+    for (int c = threadIdx.x; c < Vl; c += 256) {
+      const float x = cevp_x(zr[c]), nm = fmaxf(m, x);
+      if (nm != -INFINITY) s = s * exp2f(m - nm) + exp2f(x - nm);
+      m = nm;
+    }
+  }
+  block_maxsum(m, s, sm);
+  cevp_write_stats(m, s, zr, labels[row], v0, Vl, ignore_index, stats + (long long)row * CEVP_REC);
+}
+
+// Shards of up to 1024 * NV4 logits held in registers (cevf_rows_reg_kernel's first half: the
+// max first, then one exp2 per logit)
+template <int NV4>
+__global__ __launch_bounds__(256) void cevp_stats_reg_kernel(const float* __restrict__ z,
+                                                             const int* __restrict__ labels, int Vl, long long ld,
+                                                             int v0, int ignore_index, float* __restrict__ stats) {
+  __shared__ float sm[8];
+  const int row = blockIdx.x;
+  const float* zr = z + row * ld;
+  const int n4 = Vl >> 2;
+  float4 v[NV4];
+#pragma unroll
+  for (int j = 0; j < NV4; ++j) {
+    const int c = threadIdx.x + j * 256;
+    v[j] = c < n4 ? ((const float4*)zr)[c] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NV4; ++j) mx = fmaxf(mx, fmaxf(fmaxf(v[j].x, v[j].y), fmaxf(v[j].z, v[j].w)));
+  float m = cevp_x(mx), s = 0.f;
+  if (mx != -INFINITY) {
+#pragma unroll
+    for (int j = 0; j < NV4; ++j)
+      s += (exp2f(cevp_x(v[j].x) - m) + exp2f(cevp_x(v[j].y) - m)) +
+           (exp2f(cevp_x(v[j].z) - m) + exp2f(cevp_x(v[j].w) - m));
+  }
+  block_maxsum(m, s, sm);
+  cevp_write_stats(m, s, zr, labels[row], v0, Vl, ignore_index, stats + (long long)row * CEVP_REC);
+}
+
+__global__ __launch_bounds__(256) void cevp_grad_kernel(const float* __restrict__ z, const int* __restrict__ labels,
+                                                        const float* __restrict__ stats, int W, int R, int Vl,
+                                                        long long ld, int v0, int V, const float* __restrict__ inv,
+                                                        int ignore_index, bool vec, float* __restrict__ rowloss,
+                                                        float* __restrict__ dz, long long ldd) {
+  const int row = blockIdx.x;
+  const int lab = labels[row];
+  // every thread merges the W records itself, in rank order (uniform loads, W is a handful)
+  const float* rec = stats + (long long)row * CEVP_REC;
+  const long long rstride = (long long)R * CEVP_REC;
+  float m = rec[0], s = rec[1], tz = rec[2];
+  for (int w = 1; w < W; ++w) {
+    const float* r2 = rec + w * rstride;
+    const float m2 = r2[0], s2 = r2[1], nm = fmaxf(m, m2);
+    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + s2 * exp2f(m2 - nm);
+    m = nm;
+    tz += r2[2];
+  }
+  const float l2 = log2f(s);
+  const float lse2 = m + l2;  // log2 domain
+  const bool valid = lab != ignore_index && lab >= 0 && lab < V;
+  if (threadIdx.x == 0) rowloss[row] = valid ? (lse2 / LOG2E - tz) : 0.f;
+  if (!dz) return;
+  const float k = valid ? *inv : 0.f;
+  const float* zr = z + row * ld;
+  float* dr = dz + row * ldd;
+  const int lc = lab - v0;  // the label's column in this shard, if it has one
+  // softmax = exp2((x - m) - l2) rather than exp2(x - lse2): x - m is exact for the logits near
+  // the maximum (the only ones whose softmax is not tiny), so a row dominated by one large logit
+  // (|x| ~ 100: half an ulp of lse2 is 4e-6) keeps its 1e-7; m is the bits of the largest x itself
+#define CEVP_P(zv, col) ((exp2f((cevp_x(zv) - m) - l2) - ((col) == lc ? 1.f : 0.f)) * k)
+  if (vec) {
+    for (int c = threadIdx.x; c < Vl / 4; c += 256) {
+      const float4 v = ((const float4*)zr)[c];
+      const int b = 4 * c;
+      ((float4*)dr)[c] = make_float4(CEVP_P(v.x, b), CEVP_P(v.y, b + 1), CEVP_P(v.z, b + 2), CEVP_P(v.w, b + 3));
+    }
+  } else {
+    for (int c = threadIdx.x; c < Vl; c += 256) dr[c] = CEVP_P(zr[c], c);
+  }
+#undef CEVP_P
+}
+
+DDL_API int ddl_cevp_stats(const float* z, const int* labels, int R, int Vl, long long ld, int v0,
+                           int ignore_index, float* stats, hipStream_t s) {
+  if (R < 1 || Vl < 1 || v0 < 0) return (int)hipErrorInvalidValue;
+  const bool vec = Vl % 4 == 0 && ld % 4 == 0 && ((uintptr_t)z & 15) == 0;
+  const int n4 = Vl / 4;
+  if (vec && n4 <= 256 * 8)
+    hipLaunchKernelGGL(cevp_stats_reg_kernel<8>, dim3(R), dim3(256), 0, s, z, labels, Vl, ld, v0, ignore_index,
+                       stats);
+  else if (vec && n4 <= 256 * 16)
+    hipLaunchKernelGGL(cevp_stats_reg_kernel<16>, dim3(R), dim3(256), 0, s, z, labels, Vl, ld, v0, ignore_index,
+                       stats);
+  else if (vec && n4 <= 256 * 32)
+    hipLaunchKernelGGL(cevp_stats_reg_kernel<32>, dim3(R), dim3(256), 0, s, z, labels, Vl, ld, v0, ignore_index,
+                       stats);
+  else
+    hipLaunchKernelGGL(cevp_stats_kernel, dim3(R), dim3(256), 0, s, z, labels, Vl, ld, v0, ignore_index, vec,
+                       stats);
+  return (int)hipGetLastError();
+}
+
+// stats [W][R][4], already gathered; V is the full vocabulary (label range), dz may be null (loss only)
+DDL_API int ddl_cevp_grad(const float* z, const int* labels, const float* stats, int W, int R, int Vl, long long ld,
+                          int v0, int V, const float* inv, int ignore_index, float* rowloss, float* loss, float* dz,
+                          long long ldd, hipStream_t s) {
+  if (R < 1 || Vl < 1 || W < 1 || v0 < 0 || (long long)v0 + Vl > V) return (int)hipErrorInvalidValue;
+  const bool vec = Vl % 4 == 0 && ld % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)z & 15) == 0 &&
+                   ((uintptr_t)dz & 15) == 0;
+  hipLaunchKernelGGL(cevp_grad_kernel, dim3(R), dim3(256), 0, s, z, labels, stats, W, R, Vl, ld, v0, V, inv,
+                     ignore_index, vec, rowloss, dz, ldd);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(cevf_fold_kernel, dim3(1), dim3(256), 0, s, rowloss, R, inv, loss);
+  return (int)hipGetLastError();
+}
+
+// y = a + b: the residual added once after a row-parallel linear's all-reduce (tensor parallelism)
+__global__ void add_f32_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y,
+                               long long n, bool vec) {
+  if (vec) {
+    GSTRIDE_LOOP(i, n / 4) {
+      const float4 u = ((const float4*)a)[i], v = ((const float4*)b)[i];
+      ((float4*)y)[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+    }
+  } else {
+    GSTRIDE_LOOP(i, n) y[i] = a[i] + b[i];
+  }
+}
+
+DDL_API int ddl_add_f32(const float* a, const float* b, float* y, long long n, hipStream_t s) {
+  if (n < 1) return 0;
+  const bool vec = n % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0;
+  hipLaunchKernelGGL(add_f32_kernel, dim3(grid_for(vec ? n / 4 : n, 256, 4096)), dim3(256), 0, s, a, b, y, n, vec);
+  return (int)hipGetLastError();
+}
+
 __global__ void scale_f32_kernel(float* __restrict__ x, long long n, const float* __restrict__ g) {
   const float s = *g;
   if (s == 1.f) return;

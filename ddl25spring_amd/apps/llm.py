@@ -1,4 +1,4 @@
-"""LLaMA training over a DP x PP grid — the tutorial_1b scripts as one configurable program.
+"""LLaMA training over a DP x PP (x TP) grid — the tutorial_1b scripts as one configurable program.
 
 Covers, with one code path (reference lab/tutorial_1b):
   * intro.py                      dp=1 pp=1
@@ -6,9 +6,13 @@ Covers, with one code path (reference lab/tutorial_1b):
   * DP/weight_aggr/intro_DP_WA    dp=W, dp_mode="wa"  (averaged weights written back — fixes Q1)
   * PP/1F1B/intro_PP_1F1B(_MB)    pp=W, schedule naive | gpipe | 1f1b, micro-batches
   * PP/1F1B/intro_PP_1F1B_MP      dp x pp grid (collective group creation; verified schedule)
-Rank layout: rank = pipe * pp + stage. Every rank of a pipeline reads the same token stream
-(``skip = pipe * 3000`` as the reference), so the last stage has its targets without extra
-messages; stage weights start identical across pipelines (seeded init + broadcast).
+  * tp=T (extension)              Megatron-style tensor parallelism of the fp32 model
+                                  (parallel/tp.py): sharded blocks, vocabulary-parallel loss;
+                                  alone or with dp (not with pp, not at bf16)
+Rank layout: rank = (pipe * pp + stage) * tp + t: tensor-parallel groups are consecutive ranks, DP
+groups are the ranks of equal (stage, t). Every rank of a pipeline (and of a tp group) reads the
+same token stream (``skip = pipe * 3000`` as the reference), so the last stage has its targets
+without extra messages; stage weights start identical across pipelines (seeded init + broadcast).
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ class LLMConfig:
     micro_batches: int = 1
     dp: int = 1
     pp: int = 1
+    tp: int = 1  # tensor-parallel degree (fp32, pp = 1): world == dp * pp * tp
     schedule: str = "1f1b"
     dp_mode: str = "ga"
     iters: int = 100
@@ -59,7 +64,29 @@ _RUN_FIELDS = ("vocab_size", "dmodel", "num_heads", "n_layers", "ctx_size", "bat
 
 def _run_tag(cfg: "LLMConfig") -> str:
     """What a checkpoint must agree on to be resumable (not iters / logging / schedule)."""
-    return ",".join(f"{k}={getattr(cfg, k)}" for k in _RUN_FIELDS)
+    tag = ",".join(f"{k}={getattr(cfg, k)}" for k in _RUN_FIELDS)
+    return tag + (f",tp={cfg.tp}" if cfg.tp > 1 else "")  # older checkpoints (no tp) still resume
+
+
+def validate(cfg: "LLMConfig", world: int) -> None:
+    """Every configuration error, raised before any process group is created: all ranks see the
+    same config, so all of them raise here and none is left waiting in a collective."""
+    if world != cfg.dp * cfg.pp * cfg.tp:
+        raise ValueError(f"world {world} != dp {cfg.dp} x pp {cfg.pp} x tp {cfg.tp}")
+    if cfg.batch_size % cfg.micro_batches:
+        raise ValueError("batch_size must be divisible by micro_batches")
+    if cfg.tp > 1:
+        if cfg.pp > 1:
+            raise ValueError(f"tp={cfg.tp} with pp={cfg.pp}: tensor parallelism inside a pipeline is not supported")
+        if cfg.precision != "fp32":
+            raise ValueError(f"tp={cfg.tp} needs precision='fp32' (got {cfg.precision!r}): the sharded path "
+                             "runs the fp32 kernels only")
+        if cfg.dp > 1 and cfg.dp_mode != "ga":
+            raise ValueError(f"tp={cfg.tp} with dp_mode={cfg.dp_mode!r}: only gradient aggregation ('ga') is "
+                             "supported beside tensor parallelism")
+        from ..models.llama import _ffn_hidden
+        from ..parallel.tp import check_shardable
+        check_shardable(cfg.num_heads, _ffn_hidden(cfg.dmodel), cfg.vocab_size, cfg.tp)
 
 
 class _PinnedH2D:
@@ -92,17 +119,27 @@ def train_llm(cfg: LLMConfig, ctx, log=print, warmup: int = 0) -> dict:
     every ``cfg.ckpt_every`` steps and at the end, and a restarted job resumes from the last
     committed step: the token stream is re-positioned to that step, so a resumed run is
     bit-identical to an uninterrupted one (tests/test_checkpoint_cpu.py)."""
-    if ctx.world != cfg.dp * cfg.pp:
-        raise ValueError(f"world {ctx.world} != dp {cfg.dp} x pp {cfg.pp}")
+    validate(cfg, ctx.world)
     dev = ctx.device
-    pipe, stage, pipe_ranks, _ = grid_ranks(ctx.rank, cfg.dp, cfg.pp)
-    dp_group = ctx.new_groups("dp", [[p * cfg.pp + s for p in range(cfg.dp)] for s in range(cfg.pp)])
+    tp = cfg.tp
+    cell, t = divmod(ctx.rank, tp)  # cell = pipe * pp + stage
+    pipe, stage, pipe_ranks, _ = grid_ranks(cell, cfg.dp, cfg.pp)
+    dp_group = ctx.new_groups("dp", [[(p * cfg.pp + s) * tp + k for p in range(cfg.dp)]
+                                     for s in range(cfg.pp) for k in range(tp)])
+    tph = None
+    if tp > 1:
+        from ..parallel.tp import TPHandle, shard_llama
+        tp_group = ctx.new_groups("tp", [[c * tp + k for k in range(tp)] for c in range(cfg.dp * cfg.pp)])
+        tph = TPHandle(ctx, tp_group, tp, t)
     torch.manual_seed(cfg.seed)
     full = LLama(vocab_size=cfg.vocab_size, dmodel=cfg.dmodel, num_heads=cfg.num_heads,
                  n_layers=cfg.n_layers, ctx_size=cfg.ctx_size, precision=cfg.precision)
-    mod = split_stages(full, cfg.pp)[stage].to(dev)
-    if cfg.dp > 1:
-        broadcast_parameters(mod, ctx, src=stage, group=dp_group)  # pipeline 0's stage s is rank s
+    mod = split_stages(full, cfg.pp)[stage]
+    if tph is not None:  # every rank built the whole seeded model; keep this rank's slices of it
+        mod = shard_llama(mod, tp, t, tph)
+    mod = mod.to(dev)
+    if cfg.dp > 1:  # pipeline 0's (stage s, shard t) is rank s * tp + t
+        broadcast_parameters(mod, ctx, src=stage * tp + t, group=dp_group)
     if dev.type == "cuda" and cfg.fused_adam:
         from ..optim import FlatAdam
         # one fused Adam launch (bf16: also refreshes the bf16 weight shadow the GEMMs read; fp32:
@@ -115,8 +152,6 @@ def train_llm(cfg: LLMConfig, ctx, log=print, warmup: int = 0) -> dict:
     sync = GradBucketer(mod, ctx, group=dp_group, bucket_mb=cfg.bucket_mb,
                         flat=opt if hasattr(opt, "offsets") else None) \
         if cfg.dp > 1 and cfg.dp_mode == "ga" else None
-    if cfg.batch_size % cfg.micro_batches:
-        raise ValueError("batch_size must be divisible by micro_batches")
     mb = cfg.batch_size // cfg.micro_batches
     # stage messages in the compute precision (the reference ships fp32 micro-batch activations,
     # intro_PP_1F1B_MB.py:57)
@@ -140,7 +175,7 @@ def train_llm(cfg: LLMConfig, ctx, log=print, warmup: int = 0) -> dict:
     h2d = _PinnedH2D((cfg.batch_size, cfg.ctx_size), torch.int64, dev) if dev.type == "cuda" else None
     losses = []
 
-    use_graph = (cfg.graph and dev.type == "cuda" and cfg.dp == 1 and cfg.pp == 1
+    use_graph = (cfg.graph and dev.type == "cuda" and cfg.dp == 1 and cfg.pp == 1 and tp == 1
                  and hasattr(opt, "t_dev"))
     gstate: dict = {}
 
@@ -193,7 +228,7 @@ def train_llm(cfg: LLMConfig, ctx, log=print, warmup: int = 0) -> dict:
             loss = None
             mbs = torch.chunk(x, cfg.micro_batches)
             for i, m in enumerate(mbs):
-                l = causalLLMLoss(mod(m), m, scale=1.0 / cfg.micro_batches)
+                l = causalLLMLoss(mod(m), m, cfg.vocab_size, scale=1.0 / cfg.micro_batches, tp=tph)
                 if sync is not None and i < len(mbs) - 1:
                     with sync.no_sync():
                         l.backward()

@@ -34,10 +34,13 @@ def _ffn_hidden(d: int) -> int:
 
 
 class Block(nn.Module):
-    def __init__(self, dmodel: int, num_heads: int, ffn_hidden: int | None = None):
+    def __init__(self, dmodel: int, num_heads: int, ffn_hidden: int | None = None, tp=None):
         super().__init__()
         assert dmodel % num_heads == 0
         self.h, self.hd = num_heads, dmodel // num_heads
+        # tensor-parallel handle (parallel/tp.py: ctx, group, degree); the weights are built whole
+        # from the seed and cut by ``shard_llama``, which also sets the local head count
+        self.tp = tp
         F = ffn_hidden or _ffn_hidden(dmodel)
         self.norm1 = nn.Parameter(torch.ones(dmodel))
         self.norm2 = nn.Parameter(torch.ones(dmodel))
@@ -52,12 +55,25 @@ class Block(nn.Module):
             self.w2.mul_(1 / math.sqrt(2))
 
     def forward(self, x):  # x [B, S, D]
+        if self.tp is not None:
+            return self.forward_tp(x)
         h, x = A.rmsnorm_fork(x, self.norm1)
         qkv = A.linear(h, self.wqkv)
         att = A.causal_attention(qkv, self.h, self.hd)
         x = A.linear(att, self.wo, residual=x)
         h, x = A.rmsnorm_fork(x, self.norm2)
         return A.linear(A.swiglu(A.linear(h, self.w13)), self.w2, residual=x)
+
+    def forward_tp(self, x):
+        """The sharded block: wqkv / w13 hold this rank's heads / SwiGLU columns (column-parallel,
+        the normed input's gradient summed over the group), wo / w2 the matching input columns
+        (row-parallel: partial products summed over the group, then the residual added once)."""
+        tp = self.tp
+        h, x = A.rmsnorm_fork(x, self.norm1)
+        att = A.causal_attention(A.linear(tp.copy(h), self.wqkv), self.h, self.hd)
+        x = A.residual_add(x, tp.reduce(A.linear(att, self.wo)))
+        h, x = A.rmsnorm_fork(x, self.norm2)
+        return A.residual_add(x, tp.reduce(A.linear(A.swiglu(A.linear(tp.copy(h), self.w13)), self.w2)))
 
 
 class CausalLLama:
@@ -74,12 +90,14 @@ def _act_dtype(precision: str):
 
 
 class _Base(nn.Module):
-    def __init__(self, dmodel, num_heads, n_layers, ctx_size, device=None, ffn_hidden=None, precision="fp32"):
+    def __init__(self, dmodel, num_heads, n_layers, ctx_size, device=None, ffn_hidden=None, precision="fp32",
+                 tp=None):
         super().__init__()
         self.dmodel, self.ctx_size = dmodel, ctx_size
         self.precision = precision
         self.act_dtype = _act_dtype(precision)
-        self.layers = nn.ModuleList(Block(dmodel, num_heads, ffn_hidden) for _ in range(n_layers))
+        self.tp = tp
+        self.layers = nn.ModuleList(Block(dmodel, num_heads, ffn_hidden, tp) for _ in range(n_layers))
         if device is not None:
             self.to(device)
 
@@ -91,8 +109,8 @@ class _Base(nn.Module):
 
 class LLamaFirstStage(_Base):
     def __init__(self, vocab_size, dmodel=288, num_heads=6, device=None, n_layers=2, ctx_size=256,
-                 padding_idx=None, ffn_hidden=None, precision="fp32"):
-        super().__init__(dmodel, num_heads, n_layers, ctx_size, None, ffn_hidden, precision)
+                 padding_idx=None, ffn_hidden=None, precision="fp32", tp=None):
+        super().__init__(dmodel, num_heads, n_layers, ctx_size, None, ffn_hidden, precision, tp)
         self.vocab_size, self.padding_idx = vocab_size, padding_idx
         self.emb = nn.Parameter(torch.randn(vocab_size, dmodel) * 0.02)
         if device is not None:
@@ -106,8 +124,8 @@ class LLamaFirstStage(_Base):
 
 class LLamaStage(_Base):
     def __init__(self, dmodel=288, num_heads=6, device=None, n_layers=2, ctx_size=256, ffn_hidden=None,
-                 precision="fp32"):
-        super().__init__(dmodel, num_heads, n_layers, ctx_size, device, ffn_hidden, precision)
+                 precision="fp32", tp=None):
+        super().__init__(dmodel, num_heads, n_layers, ctx_size, device, ffn_hidden, precision, tp)
 
     def forward(self, x):
         return self.run_layers(x)
@@ -115,8 +133,8 @@ class LLamaStage(_Base):
 
 class LLamaLastStage(_Base):
     def __init__(self, vocab_size, dmodel=288, num_heads=6, device=None, n_layers=2, ctx_size=256,
-                 ffn_hidden=None, precision="fp32"):
-        super().__init__(dmodel, num_heads, n_layers, ctx_size, None, ffn_hidden, precision)
+                 ffn_hidden=None, precision="fp32", tp=None):
+        super().__init__(dmodel, num_heads, n_layers, ctx_size, None, ffn_hidden, precision, tp)
         self.vocab_size = vocab_size
         self.norm = nn.Parameter(torch.ones(dmodel))
         self.head = nn.Parameter(torch.randn(vocab_size, dmodel) * 0.02)
@@ -124,7 +142,10 @@ class LLamaLastStage(_Base):
             self.to(device)
 
     def forward(self, x):
-        return A.linear(A.rmsnorm(self.run_layers(x), self.norm), self.head)
+        h = A.rmsnorm(self.run_layers(x), self.norm)
+        if getattr(self, "tp", None) is not None:  # head cut over the vocabulary: the local logit shard
+            return A.linear(self.tp.copy(h), self.head)
+        return A.linear(h, self.head)
 
 
 class LLama(nn.Module):
@@ -173,11 +194,17 @@ def split_stages(model: LLama, n_stages: int):
     return out
 
 
-def causalLLMLoss(logits, target, vocab_size=None, ignore_index=-100, scale: float = 1.0):  # noqa: N802
+def causalLLMLoss(logits, target, vocab_size=None, ignore_index=-100, scale: float = 1.0,  # noqa: N802
+                  tp=None):
     """Next-token CE (reference name): logits[:, :-1] vs target[:, 1:]. On the device every row of
     the [B, S, V] logits goes to the fused kernel with the last position's label set to
     ``ignore_index`` (same mean, no copy of the [B, S-1, V] slice). ``scale`` (extension): a
-    constant factor such as 1 / micro-batches, folded into the kernel's normaliser."""
+    constant factor such as 1 / micro-batches, folded into the kernel's normaliser. ``tp``
+    (extension): the tensor-parallel handle of a sharded last stage, whose ``logits`` are this
+    rank's vocabulary shard of the ``vocab_size`` logits; the loss is then the vocabulary-parallel
+    CE, the same bits on every rank of the group."""
+    if tp is not None:
+        return causalLLMLossTP(logits, target, vocab_size, tp, ignore_index, scale)
     if not logits.is_cuda:
         return A.cross_entropy_vocab(logits[:, :-1].contiguous(), target[:, 1:].contiguous(), ignore_index,
                                      scale)
@@ -185,3 +212,21 @@ def causalLLMLoss(logits, target, vocab_size=None, ignore_index=-100, scale: flo
     lab[:, :-1] = target[:, 1:]
     lab[:, -1] = ignore_index
     return A.cross_entropy_vocab(logits, lab, ignore_index, scale)
+
+
+def causalLLMLossTP(logits_shard, target, vocab_size, tp, ignore_index=-100, scale: float = 1.0):  # noqa: N802
+    """``causalLLMLoss`` over a vocabulary shard [B, S, Vl] (rank ``tp.rank`` of ``tp.degree``)."""
+    from ..parallel.tp import vocab_range
+    if vocab_size is None:
+        raise ValueError("causalLLMLoss(tp=...): the full vocab_size is needed to place the shard")
+    v0, v1 = vocab_range(vocab_size, tp.degree, tp.rank)
+    if logits_shard.shape[-1] != v1 - v0:
+        raise ValueError(f"logit shard of {logits_shard.shape[-1]} columns, rank {tp.rank}/{tp.degree} of "
+                         f"vocabulary {vocab_size} holds {v1 - v0}")
+    if not logits_shard.is_cuda:
+        return A.cross_entropy_vocab_parallel(logits_shard[:, :-1].contiguous(), target[:, 1:].contiguous(), v0,
+                                              vocab_size, tp.ctx, tp.group, ignore_index, scale)
+    lab = torch.empty(target.shape, dtype=torch.int32, device=target.device)
+    lab[:, :-1] = target[:, 1:]
+    lab[:, -1] = ignore_index
+    return A.cross_entropy_vocab_parallel(logits_shard, lab, v0, vocab_size, tp.ctx, tp.group, ignore_index, scale)

@@ -288,6 +288,14 @@ def add(a, b):
     return _Add.apply(a.to(torch.bfloat16), b.to(torch.bfloat16))
 
 
+def residual_add(x, y):
+    """x + y in x's precision: where a residual cannot ride a GEMM epilogue (after a row-parallel
+    linear's all-reduce under tensor parallelism)."""
+    if x.is_cuda and _f32(x):
+        return L32.AddF32.apply(x, y.float())
+    return add(x, y)
+
+
 class _Add(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -450,6 +458,70 @@ def cross_entropy_vocab(logits, targets, ignore_index=-100, scale: float = 1.0):
     if logits.dtype != torch.bfloat16:
         logits = logits.to(torch.bfloat16)
     return _VocabCE.apply(logits, targets.to(torch.int32).contiguous(), ignore_index, float(scale))
+
+
+class _VocabParallelCERef(torch.autograd.Function):
+    """CPU twin of ``L32.VocabParallelCEF32``, from the definition: per shard the row maximum, the
+    sum of exponentials about it and the target's logit; the ranks' records all-gathered and merged
+    in rank order (so every rank holds the same loss bits); d(shard) = (softmax - onehot) / #valid."""
+
+    @staticmethod
+    def forward(ctx, shard, labels, v0, V, dctx, group, ignore_index, scale):
+        Vl = shard.shape[-1]
+        z = shard.detach().reshape(-1, Vl)
+        lab = labels.reshape(-1).long()
+        loc = lab - v0
+        mine = (lab != ignore_index) & (loc >= 0) & (loc < Vl)
+        m = z.max(dim=1).values
+        dead = torch.isinf(m) & (m < 0)
+        s = torch.where(dead.unsqueeze(1), torch.zeros_like(z), (z - m.unsqueeze(1)).exp()).sum(dim=1)
+        tz = torch.where(mine, z.gather(1, loc.clamp(0, Vl - 1).unsqueeze(1)).squeeze(1), torch.zeros_like(m))
+        rec = torch.stack([m, s, tz], dim=1)
+        allrec = dctx.all_gather_rows(rec, group) if L32.tp_world(dctx, group) > 1 else rec.unsqueeze(0)
+        M, S, T = allrec[0, :, 0], allrec[0, :, 1], allrec[0, :, 2]
+        for w in range(1, allrec.shape[0]):
+            m2, s2 = allrec[w, :, 0], allrec[w, :, 1]
+            nm = torch.maximum(M, m2)
+            none = torch.isinf(nm) & (nm < 0)
+            S = torch.where(none, torch.zeros_like(S),
+                            S * torch.where(none, torch.zeros_like(S), (M - nm).exp())
+                            + s2 * torch.where(none, torch.zeros_like(S), (m2 - nm).exp()))
+            M = nm
+            T = T + allrec[w, :, 2]
+        lse = M + S.log()
+        valid = (lab != ignore_index) & (lab >= 0) & (lab < V)
+        inv = scale / (lab != ignore_index).sum().clamp_min(1).to(z.dtype)
+        rowloss = torch.where(valid, lse - T, torch.zeros_like(lse))
+        ctx.save_for_backward(z, lse, loc, mine, valid)
+        ctx.inv, ctx.shape = inv, shard.shape
+        return rowloss.sum() * inv
+
+    @staticmethod
+    def backward(ctx, g):
+        z, lse, loc, mine, valid = ctx.saved_tensors
+        d = (z - lse.unsqueeze(1)).exp()
+        rows = torch.nonzero(mine).squeeze(1)
+        d[rows, loc[rows]] -= 1.0
+        d = d * (valid.to(z.dtype) * ctx.inv * g).unsqueeze(1)
+        return (d.view(ctx.shape),) + (None,) * 7
+
+
+def cross_entropy_vocab_parallel(logits_shard, targets, v0, vocab_size, ctx=None, group=None,
+                                 ignore_index=-100, scale: float = 1.0):
+    """``cross_entropy_vocab`` over logits split by vocabulary: this rank holds the columns
+    ``[v0, v0 + logits_shard.shape[-1])`` of the ``vocab_size`` logits of every row, the ranks of
+    ``group`` (of the ``DistContext`` ``ctx``) hold the rest in rank order. No rank forms a full
+    row: each reduces its shard to a per-row record, the records are all-gathered and merged in
+    rank order, so the returned loss is the same bits on every rank. Without a process group (or in
+    a group of one) the shard is the whole vocabulary and the same kernels run with one record."""
+    if not logits_shard.is_cuda:
+        lg = logits_shard if logits_shard.dtype in (torch.float32, torch.float64) else logits_shard.float()
+        return _VocabParallelCERef.apply(lg, targets, int(v0), int(vocab_size), ctx, group, ignore_index,
+                                         float(scale))
+    if not _f32(logits_shard):
+        raise ValueError("cross_entropy_vocab_parallel: fp32 logits only (tensor parallelism runs the fp32 path)")
+    return L32.VocabParallelCEF32.apply(logits_shard, targets.to(torch.int32).contiguous(), int(v0),
+                                        int(vocab_size), ctx, group, ignore_index, float(scale))
 
 
 # ===================================================================== image ops (NHWC, GANs)

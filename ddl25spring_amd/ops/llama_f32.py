@@ -14,6 +14,8 @@ step gives the same bits run to run.
               conv over T "pixels"); shapes neither takes run on the exact-fp32 tabular GEMM
   rmsnorm     fork variant sums the residual branch's gradient in the backward kernel
   swiglu, embedding, causal RoPE attention, vocabulary cross-entropy
+  vocabulary-parallel cross-entropy (tensor parallelism: per-shard statistics, an all-gather of the
+              ranks' records, a rank-ordered merge; the same loss bits on every rank), fp32 add
 """
 from __future__ import annotations
 
@@ -40,6 +42,9 @@ _lib.register_signatures({
     "ddl_attnf_fwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "ddl_attnf_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "ddl_cevf": [vp, vp, i32, i32, i64, vp, i32, vp, vp, vp, i64, vp],
+    "ddl_cevp_stats": [vp, vp, i32, i32, i64, i32, i32, vp, vp],
+    "ddl_cevp_grad": [vp, vp, vp, i32, i32, i32, i64, i32, i32, vp, i32, vp, vp, vp, i64, vp],
+    "ddl_add_f32": [vp, vp, vp, i64, vp],
     "ddl_scale_f32": [vp, i64, vp, vp],
 })
 
@@ -365,3 +370,95 @@ class VocabCEF32(torch.autograd.Function):
         gg = g.detach().to(torch.float32).reshape(1).contiguous()
         check(K().ddl_scale_f32(ptr(d), d.numel(), ptr(gg), stream()), "scale_f32")
         return d.view(ctx.shape), None, None, None
+
+
+# ------------------------------------------------------------- vocabulary-parallel LM loss
+CEVP_REC = 4  # floats per (rank, row) record of ddl_cevp_stats: max (log2 domain), sum, target logit, 0
+
+
+def _shard_rows(z):
+    """[R, Vl] rows with unit column stride: a column slice of a wider matrix stays where it is
+    (row stride = the wide matrix's), anything else is made contiguous."""
+    z2 = z if z.dim() == 2 else z.reshape(-1, z.shape[-1])
+    if z2.stride(1) != 1 or (z2.shape[0] > 1 and z2.stride(0) < z2.shape[1]):
+        z2 = z2.contiguous()
+    return z2
+
+
+def cevp_stats(z, lab, v0: int, ignore_index: int = -100):
+    """Per-row record of this rank's logit columns [v0, v0 + Vl): [R, 4] (see CEVP_REC)."""
+    R, Vl = z.shape
+    stats = torch.empty(R, CEVP_REC, dtype=torch.float32, device=z.device)
+    check(K().ddl_cevp_stats(ptr(z), ptr(lab), R, Vl, z.stride(0) if R > 1 else Vl, int(v0), int(ignore_index),
+                             ptr(stats), stream()), "cevp_stats")
+    return stats
+
+
+def cevp_grad(z, lab, stats, v0: int, V: int, inv, ignore_index: int = -100, want_dz: bool = True):
+    """Merge the gathered records ``stats`` [W, R, 4] in rank order -> (loss [1], rowloss [R],
+    d(shard) [R, Vl] at unit upstream scale, or None)."""
+    R, Vl = z.shape
+    W = stats.shape[0]
+    assert stats.shape == (W, R, CEVP_REC) and stats.is_contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    rowloss = torch.empty(R, dtype=torch.float32, device=z.device)
+    d = torch.empty(R, Vl, dtype=torch.float32, device=z.device) if want_dz else None
+    check(K().ddl_cevp_grad(ptr(z), ptr(lab), ptr(stats), W, R, Vl, z.stride(0) if R > 1 else Vl, int(v0), int(V),
+                            ptr(inv), int(ignore_index), ptr(rowloss), ptr(loss), ptr(d), Vl, stream()),
+          "cevp_grad")
+    return loss, rowloss, d
+
+
+def tp_world(dctx, group) -> int:
+    """Ranks that share a sharded tensor: the group's size under a process group, else 1."""
+    if dctx is None or not dctx.is_distributed:
+        return 1
+    import torch.distributed as dist
+    return dist.get_world_size(group)
+
+
+class VocabParallelCEF32(torch.autograd.Function):
+    """VocabCEF32 over a vocabulary shard [..., Vl] = columns [v0, v0 + Vl) of the [..., V] logits:
+    per-row statistics (one read of the shard), an all-gather of the ranks' records, then the merge
+    in rank order with the gradient at unit upstream scale (a second read). Same contract as
+    VocabCEF32: rescaled in place only when the upstream gradient is not 1, a second backward
+    recomputes it. The loss is the same bits on every rank of the group."""
+
+    @staticmethod
+    def forward(ctx, shard, labels, v0, V, dctx, group, ignore_index, scale):
+        lg = _shard_rows(shard)
+        lab = labels.reshape(-1)
+        inv = (lab != ignore_index).sum(dtype=torch.float32).clamp_min_(1.0).reciprocal_().reshape(1)
+        if scale != 1.0:
+            inv.mul_(scale)
+        stats = cevp_stats(lg, lab, v0, ignore_index)
+        allst = dctx.all_gather_rows(stats, group) if tp_world(dctx, group) > 1 else stats.unsqueeze(0)
+        loss, _, d = cevp_grad(lg, lab, allst, v0, V, inv, ignore_index, want_dz=ctx.needs_input_grad[0])
+        ctx.save_for_backward(lg, lab, inv, allst, d)
+        ctx.shape, ctx.ignore, ctx.v0, ctx.V, ctx.used = shard.shape, int(ignore_index), int(v0), int(V), False
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lab, inv, allst, d = ctx.saved_tensors
+        if ctx.used or d is None:  # an earlier backward already rescaled the unit-scale gradient
+            d = cevp_grad(lg, lab, allst, ctx.v0, ctx.V, inv, ctx.ignore)[2]
+        ctx.used = True
+        gg = g.detach().to(torch.float32).reshape(1).contiguous()
+        check(K().ddl_scale_f32(ptr(d), d.numel(), ptr(gg), stream()), "scale_f32")
+        return (d.view(ctx.shape),) + (None,) * 7
+
+
+class AddF32(torch.autograd.Function):
+    """a + b at fp32 (the residual after a row-parallel linear's all-reduce)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ac, bc = a.contiguous(), b.contiguous()
+        y = torch.empty_like(ac)
+        check(K().ddl_add_f32(ptr(ac), ptr(bc), ptr(y), ac.numel(), stream()), "add_f32")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, dy
