@@ -872,13 +872,22 @@ DDL_API int ddl_attnf_bwd(const float* qkv, const float* o, const float* dout, c
 // Vocabulary cross-entropy, fp32 logits [R][V] (row stride ld), int32 labels. One block per row:
 // pass 1 max / sum-exp, pass 2 d = (softmax - onehot) * (*inv); rowloss[r] = lse - z[label]
 // (0 for ignored rows, whose gradient row is zero).
+// The maximum m is kept as the logit itself and subtracted BEFORE the scaling to the log2 domain:
+//   s = sum exp2((z - m) * LOG2E),  l2 = log2(s),  softmax = exp2((z - m) * LOG2E - l2),
+//   rowloss = l2 / LOG2E + (m - z[label]).
+// z - m is exact for the logits near the maximum, the only ones whose softmax is not tiny, so a
+// confident row (label logit +30: true loss 1e-10) and a common offset (+50) keep full precision.
+// z * LOG2E - lse2 rounds z * LOG2E and lse2 at the magnitude of the logits instead (half an ulp
+// at |x| ~ 100 is 4e-6).
+__device__ __forceinline__ float ce_e2(float z, float m) { return exp2f((z - m) * LOG2E); }
+
 __device__ __forceinline__ void block_maxsum(float& m, float& s, float* sm) {
   // merge (m, s) pairs: wave level, then the 4 waves in a fixed order
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
     const float nm = fmaxf(m, m2);
-    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + s2 * exp2f(m2 - nm);
+    s = (nm == -INFINITY) ? 0.f : s * ce_e2(m, nm) + s2 * ce_e2(m2, nm);
     m = nm;
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -888,7 +897,7 @@ __device__ __forceinline__ void block_maxsum(float& m, float& s, float* sm) {
   m = sm[0]; s = sm[4];
   for (int k = 1; k < 4; ++k) {
     const float m2 = sm[k], s2 = sm[4 + k], nm = fmaxf(m, m2);
-    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + s2 * exp2f(m2 - nm);
+    s = (nm == -INFINITY) ? 0.f : s * ce_e2(m, nm) + s2 * ce_e2(m2, nm);
     m = nm;
   }
 }
@@ -901,35 +910,36 @@ __global__ __launch_bounds__(256) void cevf_rows_kernel(const float* __restrict_
   const int row = blockIdx.x;
   const float* zr = z + row * ld;
   const int lab = labels[row];
+  // running (m, s) per thread; an all -inf prefix keeps s = 0 (exp2f(-inf - -inf) is NaN)
   float m = -INFINITY, s = 0.f;
   const bool vec = (V % 4 == 0) && (ld % 4 == 0);
   if (vec) {
     for (int c = threadIdx.x; c < V / 4; c += 256) {
       const float4 v = ((const float4*)zr)[c];
-      const float x[4] = {v.x * LOG2E, v.y * LOG2E, v.z * LOG2E, v.w * LOG2E};
+      const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float nm = fmaxf(m, x[k]);
-        s = s * exp2f(m - nm) + exp2f(x[k] - nm);
+        if (nm != -INFINITY) s = s * ce_e2(m, nm) + ce_e2(x[k], nm);
         m = nm;
       }
     }
   } else {
     for (int c = threadIdx.x; c < V; c += 256) {
-      const float x = zr[c] * LOG2E, nm = fmaxf(m, x);
-      s = s * exp2f(m - nm) + exp2f(x - nm);
+      const float x = zr[c], nm = fmaxf(m, x);
+      if (nm != -INFINITY) s = s * ce_e2(m, nm) + ce_e2(x, nm);
       m = nm;
     }
   }
   block_maxsum(m, s, sm);
-  const float lse2 = m + log2f(s);  // log2 domain
+  const float l2 = log2f(s);
   const bool valid = lab != ignore_index && lab >= 0 && lab < V;
-  if (threadIdx.x == 0) rowloss[row] = valid ? (lse2 / LOG2E - zr[lab]) : 0.f;
+  if (threadIdx.x == 0) rowloss[row] = valid ? (l2 / LOG2E + (m - zr[lab])) : 0.f;
   if (!dz) return;
   const float k = valid ? *inv : 0.f;
   float* dr = dz + row * ldd;
   for (int c = threadIdx.x; c < V; c += 256) {
-    const float p = exp2f(zr[c] * LOG2E - lse2);
+    const float p = exp2f((zr[c] - m) * LOG2E - l2);
     dr[c] = (p - (c == lab ? 1.f : 0.f)) * k;
   }
 }
@@ -956,17 +966,16 @@ __global__ __launch_bounds__(256) void cevf_rows_reg_kernel(const float* __restr
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NV4; ++j) mx = fmaxf(mx, fmaxf(fmaxf(v[j].x, v[j].y), fmaxf(v[j].z, v[j].w)));
-  float m = mx * LOG2E, s = 0.f;
+  float m = mx, s = 0.f;
   if (mx != -INFINITY) {
 #pragma unroll
     for (int j = 0; j < NV4; ++j)
-      s += (exp2f(v[j].x * LOG2E - m) + exp2f(v[j].y * LOG2E - m)) +
-           (exp2f(v[j].z * LOG2E - m) + exp2f(v[j].w * LOG2E - m));
+      s += (ce_e2(v[j].x, m) + ce_e2(v[j].y, m)) + (ce_e2(v[j].z, m) + ce_e2(v[j].w, m));
   }
   block_maxsum(m, s, sm);
-  const float lse2 = m + log2f(s);
+  const float l2 = log2f(s);
   const bool valid = lab != ignore_index && lab >= 0 && lab < V;
-  if (threadIdx.x == 0) rowloss[row] = valid ? (lse2 / LOG2E - zr[lab]) : 0.f;
+  if (threadIdx.x == 0) rowloss[row] = valid ? (l2 / LOG2E + (m - zr[lab])) : 0.f;
   if (!dz) return;
   const float k = valid ? *inv : 0.f;
   float4* dr = (float4*)(dz + row * ldd);
@@ -976,10 +985,10 @@ __global__ __launch_bounds__(256) void cevf_rows_reg_kernel(const float* __restr
     if (c < n4) {
       const int b = 4 * c;
       float4 p;
-      p.x = (exp2f(v[j].x * LOG2E - lse2) - (b == lab ? 1.f : 0.f)) * k;
-      p.y = (exp2f(v[j].y * LOG2E - lse2) - (b + 1 == lab ? 1.f : 0.f)) * k;
-      p.z = (exp2f(v[j].z * LOG2E - lse2) - (b + 2 == lab ? 1.f : 0.f)) * k;
-      p.w = (exp2f(v[j].w * LOG2E - lse2) - (b + 3 == lab ? 1.f : 0.f)) * k;
+      p.x = (exp2f((v[j].x - m) * LOG2E - l2) - (b == lab ? 1.f : 0.f)) * k;
+      p.y = (exp2f((v[j].y - m) * LOG2E - l2) - (b + 1 == lab ? 1.f : 0.f)) * k;
+      p.z = (exp2f((v[j].z - m) * LOG2E - l2) - (b + 2 == lab ? 1.f : 0.f)) * k;
+      p.w = (exp2f((v[j].w - m) * LOG2E - l2) - (b + 3 == lab ? 1.f : 0.f)) * k;
       dr[c] = p;
     }
   }
@@ -1024,15 +1033,11 @@ DDL_API int ddl_cevf(const float* z, const int* labels, int R, int V, long long 
 // Vocabulary-PARALLEL cross-entropy: rank t holds the logit columns [v0, v0 + Vl) of every row,
 // z [R][Vl] (row stride ld). No rank sees a full row, so the loss is made in two launches around an
 // all-gather: ddl_cevp_stats reads the shard once and leaves one record per row,
-//   stats[r] = { local max (log2 domain), local sum of exp2, target logit if it is in the shard, 0 },
+//   stats[r] = { local max logit, local sum of exp2((z - max) * LOG2E), target logit if it is in the shard, 0 },
 // the W ranks' records are gathered to [W][R][4], and ddl_cevp_grad merges them in rank order (the
 // (m, s) merge of block_maxsum, so every rank forms the same lse bits), writes rowloss / the loss
 // and, when asked, d = (softmax - onehot) * (*inv) from a second read of the shard.
 constexpr int CEVP_REC = 4;
-
-// a logit in the log2 domain, rounded once and never contracted into the subtraction that follows:
-// x - m must be the same bits in the statistics and in the gradient pass (0 for the maximum itself)
-__device__ __forceinline__ float cevp_x(float z) { return __fmul_rn(z, LOG2E); }
 
 __device__ __forceinline__ void cevp_write_stats(float m, float s, const float* zr, int lab, int v0, int Vl,
                                                  int ignore_index, float* rec) {
@@ -1056,18 +1061,18 @@ __global__ __launch_bounds__(256) void cevp_stats_kernel(const float* __restrict
   if (vec) {
     for (int c = threadIdx.x; c < Vl / 4; c += 256) {
       const float4 v = ((const float4*)zr)[c];
-      const float x[4] = {cevp_x(v.x), cevp_x(v.y), cevp_x(v.z), cevp_x(v.w)};
+      const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float nm = fmaxf(m, x[k]);
-        if (nm != -INFINITY) s = s * exp2f(m - nm) + exp2f(x[k] - nm);
+        if (nm != -INFINITY) s = s * ce_e2(m, nm) + ce_e2(x[k], nm);
         m = nm;
       }
     }
   } else {
     for (int c = threadIdx.x; c < Vl; c += 256) {
-      const float x = cevp_x(zr[c]), nm = fmaxf(m, x);
-      if (nm != -INFINITY) s = s * exp2f(m - nm) + exp2f(x - nm);
+      const float x = zr[c], nm = fmaxf(m, x);
+      if (nm != -INFINITY) s = s * ce_e2(m, nm) + ce_e2(x, nm);
       m = nm;
     }
   }
@@ -1094,12 +1099,11 @@ __global__ __launch_bounds__(256) void cevp_stats_reg_kernel(const float* __rest
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NV4; ++j) mx = fmaxf(mx, fmaxf(fmaxf(v[j].x, v[j].y), fmaxf(v[j].z, v[j].w)));
-  float m = cevp_x(mx), s = 0.f;
+  float m = mx, s = 0.f;
   if (mx != -INFINITY) {
 #pragma unroll
     for (int j = 0; j < NV4; ++j)
-      s += (exp2f(cevp_x(v[j].x) - m) + exp2f(cevp_x(v[j].y) - m)) +
-           (exp2f(cevp_x(v[j].z) - m) + exp2f(cevp_x(v[j].w) - m));
+      s += (ce_e2(v[j].x, m) + ce_e2(v[j].y, m)) + (ce_e2(v[j].z, m) + ce_e2(v[j].w, m));
   }
   block_maxsum(m, s, sm);
   cevp_write_stats(m, s, zr, labels[row], v0, Vl, ignore_index, stats + (long long)row * CEVP_REC);
@@ -1119,23 +1123,20 @@ __global__ __launch_bounds__(256) void cevp_grad_kernel(const float* __restrict_
   for (int w = 1; w < W; ++w) {
     const float* r2 = rec + w * rstride;
     const float m2 = r2[0], s2 = r2[1], nm = fmaxf(m, m2);
-    s = (nm == -INFINITY) ? 0.f : s * exp2f(m - nm) + s2 * exp2f(m2 - nm);
+    s = (nm == -INFINITY) ? 0.f : s * ce_e2(m, nm) + s2 * ce_e2(m2, nm);
     m = nm;
     tz += r2[2];
   }
   const float l2 = log2f(s);
-  const float lse2 = m + l2;  // log2 domain
   const bool valid = lab != ignore_index && lab >= 0 && lab < V;
-  if (threadIdx.x == 0) rowloss[row] = valid ? (lse2 / LOG2E - tz) : 0.f;
+  if (threadIdx.x == 0) rowloss[row] = valid ? (l2 / LOG2E + (m - tz)) : 0.f;
   if (!dz) return;
   const float k = valid ? *inv : 0.f;
   const float* zr = z + row * ld;
   float* dr = dz + row * ldd;
   const int lc = lab - v0;  // the label's column in this shard, if it has one
-  // softmax = exp2((x - m) - l2) rather than exp2(x - lse2): x - m is exact for the logits near
-  // the maximum (the only ones whose softmax is not tiny), so a row dominated by one large logit
-  // (|x| ~ 100: half an ulp of lse2 is 4e-6) keeps its 1e-7; m is the bits of the largest x itself
-#define CEVP_P(zv, col) ((exp2f((cevp_x(zv) - m) - l2) - ((col) == lc ? 1.f : 0.f)) * k)
+  // softmax = exp2((z - m) * LOG2E - l2), m the bits of the row's largest logit (see ce_e2 above)
+#define CEVP_P(zv, col) ((exp2f(((zv) - m) * LOG2E - l2) - ((col) == lc ? 1.f : 0.f)) * k)
   if (vec) {
     for (int c = threadIdx.x; c < Vl / 4; c += 256) {
       const float4 v = ((const float4*)zr)[c];

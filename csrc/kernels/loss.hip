@@ -40,27 +40,29 @@ __global__ __launch_bounds__(256) void ce_kernel(const T* __restrict__ logits,
   float se = 0.f;
   for (int c = lane; c < ncls; c += 64) se += __expf(ld1(z + c) - mx);
   se = wave_sum(se);
-  const float lse = mx + __logf(se);
+  // lse = mx + lg is never formed: (z - mx) - lg is exact near the maximum, where mx + lg would be
+  // rounded at the magnitude of the logits (a common offset of +50: half an ulp is 2e-6)
+  const float lg = __logf(se);
   float lrow = 0.f, tsum = 1.f;
   if (targets) {
     const float* t = targets + (long long)row * ncls;
     float ts = 0.f, l = 0.f;
     for (int c = lane; c < ncls; c += 64) {
       ts += t[c];
-      l += t[c] * (lse - ld1(z + c));
+      l += t[c] * (lg - (ld1(z + c) - mx));
     }
     tsum = wave_sum(ts);
     lrow = wave_sum(l);
   } else {
     const int y = labels[row];
-    lrow = lse - ld1(z + y);
+    lrow = lg + (mx - ld1(z + y));
   }
   if (dlogits) {
     T* dz = dlogits + (long long)row * ld;
     for (int c = lane; c < ld; c += 64) {
       float gv = 0.f;
       if (c < ncls) {
-        const float p = __expf(ld1(z + c) - lse);
+        const float p = __expf((ld1(z + c) - mx) - lg);
         const float tc = targets ? targets[(long long)row * ncls + c] : (c == labels[row] ? 1.f : 0.f);
         gv = scale * (p * tsum - tc);
       }
@@ -122,9 +124,11 @@ __global__ __launch_bounds__(256) void ce_vocab_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int k = 1; k < 8; ++k) lm = fmaxf(lm, v[k]);
     const float nm = fmaxf(m, lm);
-    se = se * __expf(m - nm);
+    if (nm != -INFINITY) {  // an all -inf prefix keeps se = 0 (__expf(-inf - -inf) is NaN)
+      se = se * __expf(m - nm);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+      for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+    }
     m = nm;
   }
   // combine (m, se) across the block
@@ -141,10 +145,10 @@ __global__ __launch_bounds__(256) void ce_vocab_kernel(const bf16_t* __restrict_
   for (int i = 1; i < 4; ++i) M = fmaxf(M, sm[0][i]);
   float SE = 0.f;
   for (int i = 0; i < 4; ++i) SE += sm[1][i] * __expf(sm[0][i] - M);
-  const float lse = M + __logf(SE);
+  const float lg = __logf(SE);  // lse = M + lg is never formed: (z - M) - lg is exact near the maximum
   const int y = labels[row];
-  const bool ign = (y == ignore_index);
-  if (tid == 0 && loss && !ign) atomicAdd(loss, (lse - bf2f(z[y])) * scale);
+  const bool ign = (y == ignore_index) || y < 0 || y >= V;  // out of range: a zero row, like ddl_cevf
+  if (tid == 0 && loss && !ign) atomicAdd(loss, (lg + (M - bf2f(z[y]))) * scale);
   if (dlogits) {
     bf16_t* dz = dlogits + (long long)row * ld;
     for (int c = tid * 8; c < V; c += 256 * 8) {
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void ce_vocab_kernel(const bf16_t* __restrict_
       unpack8(*(const i4v*)(z + c), v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float p = __expf(v[k] - lse);
+        const float p = __expf((v[k] - M) - lg);
         v[k] = ign ? 0.f : scale * (p - ((c + k) == y ? 1.f : 0.f));
       }
       *(i4v*)(dz + c) = pack8(v);
@@ -206,9 +210,11 @@ __global__ __launch_bounds__(256) void ce_vocab_fused_kernel(const bf16_t* __res
 #pragma unroll
       for (int k = 1; k < 8; ++k) lm = fmaxf(lm, v[k]);
       const float nm = fmaxf(m, lm);
-      se = se * __expf(m - nm);
+      if (nm != -INFINITY) {  // an all -inf prefix keeps se = 0 (__expf(-inf - -inf) is NaN)
+        se = se * __expf(m - nm);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+        for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+      }
       m = nm;
     }
   }
@@ -225,9 +231,9 @@ __global__ __launch_bounds__(256) void ce_vocab_fused_kernel(const bf16_t* __res
   for (int i = 1; i < 4; ++i) M = fmaxf(M, sm[0][i]);
   float SE = 0.f;
   for (int i = 0; i < 4; ++i) SE += sm[1][i] * __expf(sm[0][i] - M);
-  const float lse = M + __logf(SE);
-  const bool ign = (y == ignore_index);
-  if (tid == 0 && !ign) atomicAdd(loss, (lse - bf2f(z[y])) * sc);
+  const float lg = __logf(SE);  // lse = M + lg is never formed: (z - M) - lg is exact near the maximum
+  const bool ign = (y == ignore_index) || y < 0 || y >= V;  // out of range: a zero row, like ddl_cevf
+  if (tid == 0 && !ign) atomicAdd(loss, (lg + (M - bf2f(z[y]))) * sc);
   bf16_t* dz = dlogits + (long long)row * ld;
 #pragma unroll
   for (int i = 0; i < CE_RC; ++i) {
@@ -236,7 +242,8 @@ __global__ __launch_bounds__(256) void ce_vocab_fused_kernel(const bf16_t* __res
       float v[8];
       unpack8(raw[i], v);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = ign ? 0.f : sc * (__expf(v[k] - lse) - ((c + k) == y ? 1.f : 0.f));
+      for (int k = 0; k < 8; ++k)
+        v[k] = ign ? 0.f : sc * (__expf((v[k] - M) - lg) - ((c + k) == y ? 1.f : 0.f));
       *(i4v*)(dz + c) = pack8(v);
     }
   }
@@ -275,8 +282,12 @@ DDL_API int ddl_ce_vocab_scale(void* x, long long n, const float* g, hipStream_t
 
 // ---------------------------------------------------------------------------------------------
 // Split LM-head CE for autograd without host syncs or extra passes over the [rows, V] logits:
-//   fwd : lse[row] and loss += (lse - z_y) * (*inv)          (inv = 1 / #non-ignored rows, device)
+//   fwd : lse[row] = { M, log(sum exp(z - M)) } and loss += (log(sum) + (M - z_y)) * (*inv)
+//                                                          (inv = 1 / #non-ignored rows, device)
 //   bwd : dz = (*g) * (*inv) * (softmax(z) - onehot(y))      (g = upstream grad, device scalar)
+// lse is [R][2]: the row maximum and the log of the sum about it, kept apart so that the backward
+// forms softmax = exp((z - M) - log(sum)); M + log(sum) as one float is rounded at the magnitude of
+// the logits, and a confident row (softmax of the label 1 - 3e-6) loses its gradient to that.
 // so the mean normaliser and the upstream scale (e.g. 1/micro-batches) never leave the device, and
 // the gradient is produced in backward, in one read of z and one write of dz.
 __global__ __launch_bounds__(256) void ce_vocab_lse_kernel(const bf16_t* __restrict__ logits,
@@ -295,9 +306,11 @@ __global__ __launch_bounds__(256) void ce_vocab_lse_kernel(const bf16_t* __restr
 #pragma unroll
     for (int k = 1; k < 8; ++k) lm = fmaxf(lm, v[k]);
     const float nm = fmaxf(m, lm);
-    se = se * __expf(m - nm);
+    if (nm != -INFINITY) {  // an all -inf prefix keeps se = 0 (__expf(-inf - -inf) is NaN)
+      se = se * __expf(m - nm);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+      for (int k = 0; k < 8; ++k) se += __expf(v[k] - nm);
+    }
     m = nm;
   }
 #pragma unroll
@@ -314,10 +327,11 @@ __global__ __launch_bounds__(256) void ce_vocab_lse_kernel(const bf16_t* __restr
   for (int i = 1; i < 4; ++i) M = fmaxf(M, sm[0][i]);
   float SE = 0.f;
   for (int i = 0; i < 4; ++i) SE += sm[1][i] * __expf(sm[0][i] - M);
-  const float lse = M + __logf(SE);
-  lse_out[row] = lse;
+  const float lg = __logf(SE);
+  lse_out[2 * row] = M;
+  lse_out[2 * row + 1] = lg;
   const int y = labels[row];
-  if (y != ignore_index) atomicAdd(loss, (lse - bf2f(z[y])) * (*inv));
+  if (y != ignore_index && y >= 0 && y < V) atomicAdd(loss, (lg + (M - bf2f(z[y]))) * (*inv));
 }
 
 __global__ __launch_bounds__(256) void ce_vocab_grad_kernel(const bf16_t* __restrict__ logits,
@@ -329,15 +343,15 @@ __global__ __launch_bounds__(256) void ce_vocab_grad_kernel(const bf16_t* __rest
                                                             bf16_t* __restrict__ dlogits) {
   const int row = blockIdx.x;
   const int y = labels[row];
-  const bool ign = y == ignore_index;
-  const float sc = (*g) * (*inv), L = lse[row];
+  const bool ign = y == ignore_index || y < 0 || y >= V;
+  const float sc = (*g) * (*inv), M = lse[2 * row], lg = lse[2 * row + 1];
   const bf16_t* z = logits + (long long)row * ld;
   bf16_t* dz = dlogits + (long long)row * ld;
   for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
     float v[8];
     unpack8(*(const i4v*)(z + c), v);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = ign ? 0.f : sc * (__expf(v[k] - L) - ((c + k) == y ? 1.f : 0.f));
+    for (int k = 0; k < 8; ++k) v[k] = ign ? 0.f : sc * (__expf((v[k] - M) - lg) - ((c + k) == y ? 1.f : 0.f));
     *(i4v*)(dz + c) = pack8(v);
   }
 }
@@ -596,13 +610,13 @@ __global__ __launch_bounds__(256) void head_train_kernel(HeadArgs a) {
       if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
     }
     const float e = on ? __expf(z - mx) : 0.f;
-    const float lse = mx + __logf(wave_sum(e));
+    const float lg = __logf(wave_sum(e));  // lse = mx + lg is never formed (rounded at the logits' magnitude)
     const float zy = __shfl(z, y, 64);
-    const float d = on ? a.scale * (__expf(z - lse) - (lane == y ? 1.f : 0.f)) : 0.f;
+    const float d = on ? a.scale * (__expf((z - mx) - lg) - (lane == y ? 1.f : 0.f)) : 0.f;
     zl[lane] = d;
     a.dlog[rowg * 64 + lane] = d;
     if (lane == 0) {
-      atomicAdd(a.loss + g, (lse - zy) * a.scale);
+      atomicAdd(a.loss + g, (lg + (mx - zy)) * a.scale);
       if (a.correct && am == y) atomicAdd(a.correct + g, 1);
     }
   }

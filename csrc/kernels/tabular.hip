@@ -238,19 +238,20 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(const float* __restrict__ l
     se += __expf(v - mx);
     const float t = targets ? targets[(long long)row * C + c] : (labels[row] == c ? 1.f : 0.f);
     tsum += t;
-    tl += t * v;
+    if (t != 0.f) tl += t * (v - mx);  // about the maximum; a masked (-inf) logit off the target: 0, not 0 * -inf
   }
   se = wave_sum(se);
   tsum = wave_sum(tsum);
   tl = wave_sum(tl);
-  const float lse = mx + __logf(se);
   if (dlogits) {
     for (int c = lane; c < C; c += 64) {
       const float t = targets ? targets[(long long)row * C + c] : (labels[row] == c ? 1.f : 0.f);
       dlogits[(long long)row * C + c] = (__expf(lg[c] - mx) / se * tsum - t) / (float)M;
     }
   }
-  if (lane == 0) atomicAdd(loss, (tsum * lse - tl) / (float)M);
+  // sum t (lse - z) = sum(t) log(se) - sum t (z - mx): lse = mx + log(se) itself is rounded at the
+  // magnitude of the logits (a common offset of +50: 2e-6)
+  if (lane == 0) atomicAdd(loss, (tsum * __logf(se) - tl) / (float)M);
 }
 
 DDL_API int ddl_ce_f32(const float* logits, const float* targets, const int* labels, int M, int C,

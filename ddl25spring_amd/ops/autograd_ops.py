@@ -409,7 +409,7 @@ class _VocabCE(torch.autograd.Function):
         # the fused loss + gradient pass writes a [R, V] gradient: only worth it when one is needed
         # (no_grad / eval forwards keep just the per-row log-sum-exp)
         if V > CE_FUSED_MAX_V or not ctx.needs_input_grad[0]:
-            lse = torch.empty(R, dtype=torch.float32, device=lg.device)
+            lse = torch.empty(R, 2, dtype=torch.float32, device=lg.device)  # (row max, log of the sum about it)
             check(K().ddl_ce_vocab_lse(ptr(lg), ptr(lab), R, V, V, ptr(inv), int(ignore_index), ptr(loss),
                                        ptr(lse), stream()), "ce_vocab_lse")
             d = None
@@ -463,7 +463,9 @@ def cross_entropy_vocab(logits, targets, ignore_index=-100, scale: float = 1.0):
 class _VocabParallelCERef(torch.autograd.Function):
     """CPU twin of ``L32.VocabParallelCEF32``, from the definition: per shard the row maximum, the
     sum of exponentials about it and the target's logit; the ranks' records all-gathered and merged
-    in rank order (so every rank holds the same loss bits); d(shard) = (softmax - onehot) / #valid."""
+    in rank order (so every rank holds the same loss bits); d(shard) = (softmax - onehot) / #valid.
+    As in the kernels the merged maximum M is subtracted first, softmax = exp((z - M) - log S) and
+    rowloss = log S + (M - target): lse = M + log S would be rounded at the magnitude of the logits."""
 
     @staticmethod
     def forward(ctx, shard, labels, v0, V, dctx, group, ignore_index, scale):
@@ -488,18 +490,18 @@ class _VocabParallelCERef(torch.autograd.Function):
                             + s2 * torch.where(none, torch.zeros_like(S), (m2 - nm).exp()))
             M = nm
             T = T + allrec[w, :, 2]
-        lse = M + S.log()
+        logS = S.log()
         valid = (lab != ignore_index) & (lab >= 0) & (lab < V)
         inv = scale / (lab != ignore_index).sum().clamp_min(1).to(z.dtype)
-        rowloss = torch.where(valid, lse - T, torch.zeros_like(lse))
-        ctx.save_for_backward(z, lse, loc, mine, valid)
+        rowloss = torch.where(valid, logS + (M - T), torch.zeros_like(logS))
+        ctx.save_for_backward(z, M, logS, loc, mine, valid)
         ctx.inv, ctx.shape = inv, shard.shape
         return rowloss.sum() * inv
 
     @staticmethod
     def backward(ctx, g):
-        z, lse, loc, mine, valid = ctx.saved_tensors
-        d = (z - lse.unsqueeze(1)).exp()
+        z, M, logS, loc, mine, valid = ctx.saved_tensors
+        d = ((z - M.unsqueeze(1)) - logS.unsqueeze(1)).exp()
         rows = torch.nonzero(mine).squeeze(1)
         d[rows, loc[rows]] -= 1.0
         d = d * (valid.to(z.dtype) * ctx.inv * g).unsqueeze(1)

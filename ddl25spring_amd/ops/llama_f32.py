@@ -373,7 +373,7 @@ class VocabCEF32(torch.autograd.Function):
 
 
 # ------------------------------------------------------------- vocabulary-parallel LM loss
-CEVP_REC = 4  # floats per (rank, row) record of ddl_cevp_stats: max (log2 domain), sum, target logit, 0
+CEVP_REC = 4  # floats per (rank, row) record of ddl_cevp_stats: max logit, sum of exp(z - max), target logit, 0
 
 
 def _shard_rows(z):

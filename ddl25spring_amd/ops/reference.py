@@ -290,8 +290,7 @@ def channel_sum(x, out):
 def ce_fwd_bwd(logits, labels, targets, ncls, scale, loss=None, correct=None, want_grad=True):
     # logits [G, N, ld]
     z = logits.float()[..., :ncls]
-    lse = torch.logsumexp(z, -1, keepdim=True)
-    logp = z - lse
+    logp = F.log_softmax(z, -1)  # (z - max) - log(sum): z - logsumexp(z) rounds at the logits' magnitude
     if targets is not None:
         t = targets.float()
         lrow = -(t * logp).sum(-1)
