@@ -6,6 +6,9 @@
 //   ddl_clip_scales   : norms[k] = sqrt(sq[k]), cs[k] = coeff[k] * min(1, C / norms[k]);
 //                       cs[k] = 0 for a row whose squared norm is NaN / Inf
 //   ddl_clipped_sum   : delta[i] (+)= sum_k cs[k] * fl32(x_ki - c_i), rows with cs[k] == 0 not read
+//   ddl_rlr_sum       : the clipped sum and the per-coordinate sign vote of the robust learning rate
+//                       in one read of the rows; delta[i] negated where |votes[i]| < theta
+//   ddl_rlr_flip      : that negation on its own, after the cross-rank sums of delta and votes
 //   ddl_apply_update  : w[i] = c[i] + delta[i] + std * z_i, z_i ~ N(0, 1) from Philox
 //   ddl_cc_step       : one centered-clipping iteration, v += sum_k cs[k] * fl32(x_k - ctr), fused
 //                       with the next iteration's squared norms (up to 16 rows, see there)
@@ -412,6 +415,77 @@ DDL_API int ddl_clipped_sum(const float* X, long long ld, const float* center, c
   if (G < 0 || n < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(clipped_sum_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, X, ld,
                      center, cs, G, n, out, accumulate);
+  return (int)hipGetLastError();
+}
+
+// The robust learning rate (RLR: Ozdayi, Kantarcioglu, Gel, AAAI 2021): a per-coordinate sign vote
+// over the client updates, in the same single read of the rows as the clipped sum. With
+// u_ki = fl32(x_ki - c_i) over the rows with cs[k] != 0 (the others are not read and do not vote):
+//   delta[i] = sum_k cs[k] * u_ki            clipped_sum_kernel's loop: the same order and roundings
+//   s_i      = sum_k sgn(u_ki)               sgn(+-0) = sgn(NaN) = 0; unweighted, held as fp32: sums
+//                                            of at most G < 2^24 values in {-1, 0, 1}, exact in any order
+// theta < 0, the partial mode of several ranks: delta and votes go out as they are (votes required).
+// theta >= 0, the final mode: delta[i] is negated where |s_i| < theta, votes written when given.
+// Nothing is held per row, so G is bounded by memory only: (G + 2) words per coordinate, one more
+// with votes.
+__global__ void rlr_sum_kernel(const float* __restrict__ X, long long ld, const float* c,
+                               const float* __restrict__ cs, int G, long long n, float theta, float* delta,
+                               float* votes) {
+  const bool vec = (ld % 4) == 0 &&
+                   (((uintptr_t)delta | (uintptr_t)votes | (uintptr_t)X | (uintptr_t)c) & 15) == 0;
+  quad_stream(n, vec, [&](long long e, auto w) {
+#pragma clang fp contract(off)
+    constexpr int W = decltype(w)::value;
+    fvec<W> acc = fzero<W>(), s = fzero<W>();
+    const fvec<W> m = c ? ldv<W>(c + e) : fzero<W>();
+    for (int g = 0; g < G; ++g) {
+      const float k = cs[g];
+      if (k == 0.f) continue;  // dropped row (or zero weight): not read, no vote
+      const fvec<W> v = ldv<W>(X + g * ld + e);
+#pragma unroll
+      for (int i = 0; i < W; ++i) {
+        const float u = v[i] - m[i];
+        acc[i] = acc[i] + k * u;
+        s[i] = s[i] + (float)((u > 0.f) - (u < 0.f));  // both false for +-0 and NaN
+      }
+    }
+    if (theta >= 0.f) {
+#pragma unroll
+      for (int i = 0; i < W; ++i)
+        if (fabsf(s[i]) < theta) acc[i] = -acc[i];
+    }
+    stv<W>(delta + e, acc);
+    if (votes) stv<W>(votes + e, s);
+  });
+}
+
+DDL_API int ddl_rlr_sum(const float* X, long long ld, const float* center, const float* cs, int G, long long n,
+                        float theta, float* delta, float* votes, hipStream_t s) {
+  if (G < 0 || G >= (1 << 24) || n < 1 || !delta || theta != theta || (theta < 0.f && !votes))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(rlr_sum_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, X, ld, center, cs, G,
+                     n, theta, delta, votes);
+  return (int)hipGetLastError();
+}
+
+// delta[i] = -delta[i] where |votes[i]| < theta: the second half of the partial mode, after the
+// cross-rank sums of both vectors. Three words per coordinate.
+__global__ void rlr_flip_kernel(float* delta, const float* __restrict__ votes, long long n, float theta) {
+  const bool vec = (((uintptr_t)delta | (uintptr_t)votes) & 15) == 0;
+  quad_stream(n, vec, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    fvec<W> d = ldv<W>(delta + e);
+    const fvec<W> s = ldv<W>(votes + e);
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+      if (fabsf(s[i]) < theta) d[i] = -d[i];
+    stv<W>(delta + e, d);
+  });
+}
+
+DDL_API int ddl_rlr_flip(float* delta, const float* votes, long long n, float theta, hipStream_t s) {
+  if (n < 1 || !delta || !votes || !(theta >= 0.f)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(rlr_flip_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, delta, votes, n, theta);
   return (int)hipGetLastError();
 }
 

@@ -23,10 +23,10 @@ class FLConfig:
     rounds: int = 10
     iid: bool = True
     seed: int = 10
-    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | bulyan | clipped | centered_clip | geomed | secagg
+    aggregator: str = "mean"       # mean | median | trimmed_mean | krum | multi_krum | bulyan | clipped | centered_clip | geomed | secagg | rlr
     trim: float = 0.1
     krum_f: int = 1                # krum / multi_krum / bulyan: the Byzantine clients assumed
-    clip_norm: float | None = None  # clipped / secagg: L2 bound C on every client update (default: 1.0 / none)
+    clip_norm: float | None = None  # clipped / secagg / rlr: L2 bound C on every client update (default: 1.0 / none / none)
     noise_multiplier: float = 0.0  # clipped: DP-FedAvg noise std = z * C / K (needs uniform weighting)
     agg_weighting: str = "samples"  # clipped / centered_clip / geomed: samples (n_k / n) | uniform (1 / K)
     dp_delta: float = 1e-5         # the delta of the epsilon reported per round when noise is on
@@ -34,6 +34,7 @@ class FLConfig:
     cc_iters: int = 3              # centered_clip: clipping iterations per round
     gm_iters: int = 3              # geomed: smoothed Weiszfeld iterations per round
     gm_nu: float = 1e-6            # geomed: the floor of a distance in the weights a_k / max(nu, d_k)
+    rlr_theta: float = 0.0         # rlr: a coordinate on which fewer than theta clients (net) agree is flipped
     secagg_bits: int = 20          # secagg: fractional bits of the fixed-point uploads, 8..30
     secagg_min_survivors: int = 2  # secagg: a round with fewer reporting clients is aborted
     prox_mu: float = 0.0           # FedProx: mu of the proximal term mu/2 |w - w_global|^2 (0 = off)
@@ -46,10 +47,14 @@ class FLConfig:
     compress_ratio: float = 0.1    # topk: fraction of the coordinates every client sends
     compress_bits: int = 4         # quant: bits per coordinate, 2..8
     error_feedback: bool = True    # keep what the codec dropped per client and add it back next round
-    attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider | alie | ipm
+    attack: str | None = None      # label_flip | sign_flip | gaussian | free_rider | alie | ipm | backdoor
     attack_z: float | None = None  # alie: z of mu - z * sigma (default: z_max of the round's n and f)
     attack_eps: float = 0.5        # ipm: eps of -eps * mu
     attack_knowledge: str = "benign"  # alie / ipm: statistics over the benign rows | the colluders' own
+    backdoor_target: int = 0       # backdoor: the class every triggered input should go to
+    backdoor_fraction: float = 0.5  # backdoor: share of a malicious client's samples replaced by triggered copies
+    backdoor_patch: int = 4        # backdoor: side of the trigger square in the bottom-right corner
+    backdoor_boost: float = 1.0    # backdoor: model replacement, the malicious update scaled by this
     malicious: int = 0             # number of malicious clients (ids 0..malicious-1)
     dropout: float = 0.0
     stragglers: float = 0.0        # probability a sampled client is slow
@@ -77,20 +82,28 @@ def build_server(cfg: FLConfig, ctx):
         akw = {"z": cfg.attack_z, "knowledge": cfg.attack_knowledge}
     elif cfg.attack == "ipm":
         akw = {"eps": cfg.attack_eps, "knowledge": cfg.attack_knowledge}
+    elif cfg.attack == "backdoor":
+        akw = {"target": cfg.backdoor_target, "poison_fraction": cfg.backdoor_fraction, "patch": cfg.backdoor_patch,
+               "boost": cfg.backdoor_boost, "seed": cfg.seed}
     attack = make_attack(cfg.attack, list(range(cfg.malicious)), **akw) if cfg.attack else None
+    backdoor_test = None
+    if cfg.attack == "backdoor":  # the data is poisoned here, on the host, identically on every rank
+        train, parts = attack.poison(train, parts)
+        backdoor_test = DeviceImageDataset(attack.triggered_test(test), ctx.device)
     algo = {"fedavg": FedAvg, "fedsgd": FedSGD, "fedsgd_weight": FedSgdWeight,
             "scaffold": Scaffold}[cfg.algorithm]
     secure = cfg.aggregator.lower() in ("secagg", "secure", "secure_mean")
-    # without --clip-norm: the clipped mean bounds at 1.0, secure aggregation does not clip
-    clip = cfg.clip_norm if cfg.clip_norm is not None else (float("inf") if secure else 1.0)
+    rlr = cfg.aggregator.lower() in ("rlr", "robust_lr")
+    # without --clip-norm: the clipped mean bounds at 1.0, secure aggregation and rlr do not clip
+    clip = cfg.clip_norm if cfg.clip_norm is not None else (float("inf") if secure or rlr else 1.0)
     kw = dict(lr=cfg.lr, client_fraction=cfg.client_fraction, seed=cfg.seed,
               test_data=DeviceImageDataset(test, ctx.device), aggregator=cfg.aggregator,
               agg_kwargs={"trim": cfg.trim, "f": cfg.krum_f, "clip": clip, "frac_bits": cfg.secagg_bits,
                           "min_survivors": cfg.secagg_min_survivors,
                           "noise_multiplier": cfg.noise_multiplier, "seed": cfg.seed,
                           "weighting": cfg.agg_weighting, "tau": cfg.cc_tau, "iters": cfg.cc_iters,
-                          "gm_iters": cfg.gm_iters, "gm_nu": cfg.gm_nu},
-              attack=attack, ctx=ctx,
+                          "gm_iters": cfg.gm_iters, "gm_nu": cfg.gm_nu, "theta": cfg.rlr_theta},
+              attack=attack, ctx=ctx, backdoor_test=backdoor_test,
               dropout=cfg.dropout, stragglers=cfg.stragglers,
               straggler_slowdown=cfg.straggler_slowdown, deadline=cfg.deadline, prox_mu=cfg.prox_mu)
     if cfg.server_opt:
@@ -133,6 +146,8 @@ def run_fl(cfg: FLConfig, ctx, log=print):
                 rec["epsilon"] = privacy.epsilon(i + 1, server.K / server.N, cfg.noise_multiplier, cfg.dp_delta)
             if up is not None and i < len(up):  # bytes the round's reporting clients sent up
                 rec["uplink_bytes"] = up[i]
+            if i < len(res.backdoor_accuracy):  # the attack success rate on the triggered test set
+                rec["backdoor_accuracy"] = res.backdoor_accuracy[i]
             if secure:  # host-known: the sampled clients, those that reported, whether the server opened
                 gone = sum(len(lst[i]) for lst in (server.dropped, server.straggled) if i < len(lst))
                 rec.update(secagg_cohort=server.K, secagg_survivors=server.K - gone,

@@ -20,6 +20,9 @@
 * ``ClippedMean`` — norm bounding (Sun et al. 2019) and DP-FedAvg (McMahan et al. 2018)
   [north-star]: each update clipped to L2 norm C, then the weighted mean, optionally plus Gaussian
   noise; streaming kernels (clip_agg.hip), the mean's cross-rank route, any number of clients.
+* ``RobustLR`` — the robust learning rate (Ozdayi et al. 2021) [north-star], aimed at backdoors: the
+  clipped mean with a per-coordinate sign vote formed in the same pass over the rows (rlr_sum); where
+  too few clients agree the aggregate is negated.
 * ``CenteredClip`` — centered clipping (Karimireddy et al. 2021) [north-star]: iterated clipping
   around a carried estimate of the aggregate update; the clipped mean's ops, or one fused step kernel
   per iteration on a single GPU.
@@ -194,6 +197,84 @@ class ClippedMean(MeanAggregator):
 
     def load_state_dict(self, sd: dict) -> None:
         self.rounds, self.last_k = int(sd["rounds"]), int(sd.get("last_k", 0))
+
+
+class RobustLR(ClippedMean):
+    """The robust learning rate, RLR (Ozdayi, Kantarcioglu, Gel, AAAI 2021) [north-star], a defence
+    aimed at backdoors: per coordinate the reporting clients vote with the sign of their update,
+
+        s_i = sum_k sgn(fl32(x_ki - c_i)),    theta_r = min(theta, K_r)
+        out_i = c_i + lr_i * delta_i,         lr_i = -1 where |s_i| < theta_r, else +1
+
+    with ``delta`` the clipped mean's sum: where fewer than theta_r clients (net) agree on a
+    direction, the server moves against the aggregate instead of with it. Votes are unweighted, one
+    per reporting client; K_r counts the reporting clients of all ranks, so a round thinned by
+    dropout does not flip everything. ``theta = 0`` is exactly ``ClippedMean``.
+
+    Everything else is ``ClippedMean``'s: the calling convention, norms, clip scales (``clip`` = inf
+    by default: no clipping), a NaN / Inf row dropped with weight 0 (it does not vote either), the
+    noise, the state. So the paper's RLR + clipping + noise costs what the clipped mean costs. The
+    rule has no server step size of its own; it composes with a server optimizer like every
+    ``takes_center`` rule.
+
+    Two routes. One rank, ``fuse``: ``Fn.rlr_sum`` in final mode forms the sum and the votes and
+    applies the flip in the clipped sum's single read of the rows, (G + 2) floats per coordinate.
+    Several ranks, or ``fuse = False``: ``Fn.rlr_sum`` in partial mode, then ``delta`` and the votes
+    each take the mean's cross-rank route (the votes are small integers in fp32: exact in any order),
+    then ``Fn.rlr_flip``; a rank without rows contributes zeros to both. On one rank the two routes
+    give the same bits.
+
+    ``keep_votes`` (off by default): the fused route writes the votes too, ``last_votes`` is that
+    device vector [P] (valid until the next call) and ``last_flipped`` counts the flipped
+    coordinates when it is read -- the only host synchronisation."""
+    name = "rlr"
+    fuse = True         # the one-pass final mode on a single rank; off for A/B runs and tests
+    keep_votes = False
+
+    def __init__(self, theta: float, clip: float = math.inf, noise_multiplier: float = 0.0, seed: int = 0,
+                 weighting: str = "samples", ordered: bool | None = None):
+        super().__init__(clip, noise_multiplier, seed, weighting, ordered)
+        self.theta = float(theta)
+        if not self.theta >= 0.0:
+            raise ValueError(f"theta must be >= 0, got {theta}")
+        if self.noise_multiplier > 0.0 and not math.isfinite(self.clip):
+            raise ValueError("noise_multiplier > 0 needs a finite clip: the noise is scaled by it")
+        self.last_theta = 0.0  # theta_r of the last round
+        self._votes = None
+
+    def _clipped(self, ctx, rows, coeffs, out, center, K_r: int):
+        G, P = rows.shape
+        dev = out.device
+        buf = lambda name: self._tables.get((name, P, dev), lambda: torch.empty(P, dtype=torch.float32, device=dev))
+        delta = buf("delta")
+        theta_r = self.last_theta = min(self.theta, float(K_r))
+        cs = self._norms = None
+        if G:
+            rows, coeffs, cs = self._prepare(rows, coeffs, center, G, K_r, dev)
+        fused = self.fuse and not ctx.is_distributed
+        votes = buf("votes") if self.keep_votes or not fused else None
+        if cs is None:  # no rows on this rank: zeros, which flip to zeros
+            delta.zero_()
+            if votes is not None:
+                votes.zero_()
+        else:
+            Fn.rlr_sum(rows, center, cs, delta, votes, theta_r if fused else None)
+        if not fused:
+            self.cross_rank_sum(ctx, delta)
+            self.cross_rank_sum(ctx, votes)
+            Fn.rlr_flip(delta, votes, theta_r)
+        self._votes = votes if self.keep_votes else None
+        return self._finish(out, center, delta, K_r)
+
+    @property
+    def last_votes(self):
+        """s [P] of the last round on the device, summed over all ranks (None without ``keep_votes``)."""
+        return self._votes
+
+    @property
+    def last_flipped(self):
+        """The coordinates the last round flipped (syncs the device; None without ``keep_votes``)."""
+        return None if self._votes is None else int((self._votes.abs() < self.last_theta).sum())
 
 
 class CenteredClip(ClippedMean):
@@ -809,6 +890,9 @@ def make_aggregator(name: str, **kw):
     if name in ("clipped", "clipped_mean", "norm_clip"):
         return ClippedMean(kw.get("clip", 1.0), kw.get("noise_multiplier", 0.0), kw.get("seed", 0),
                            kw.get("weighting", "samples"))
+    if name in ("rlr", "robust_lr"):
+        return RobustLR(kw.get("theta", 0.0), kw.get("clip", math.inf), kw.get("noise_multiplier", 0.0),
+                        kw.get("seed", 0), kw.get("weighting", "samples"))
     if name in ("centered_clip", "cc"):
         return CenteredClip(kw.get("tau", 1.0), kw.get("iters", 3), kw.get("weighting", "samples"),
                             kw.get("warm_start", True))

@@ -45,7 +45,8 @@ class FederatedBase:
                  init_fn=None, eval_every: int = 1, eval_limit: int | None = None, name=None,
                  agg_kwargs=None, dropout: float = 0.0, stragglers: float = 0.0,
                  straggler_slowdown: float = 4.0, deadline: float | None = None, prox_mu: float = 0.0,
-                 server_opt=None, server_opt_kwargs=None, compressor=None, compressor_kwargs=None):
+                 server_opt=None, server_opt_kwargs=None, compressor=None, compressor_kwargs=None,
+                 backdoor_test=None):
         # [NS] heterogeneity: FedProx's proximal term mu/2 |w - w_global|^2 in every client's
         # objective (Li et al. 2020), and a FedOpt server optimizer stepping w_global with the
         # aggregate update as pseudo-gradient (Reddi et al. 2021); both off by default
@@ -79,6 +80,11 @@ class FederatedBase:
         self.data.set_input_spec(self.net.input_spec)
         if self.test_data is not None:
             self.test_data.set_input_spec(self.net.input_spec)
+        # [NS] the triggered test set of a backdoor attack (``Backdoor.triggered_test``): the server
+        # model's accuracy on it is the attack success rate, reported beside the test accuracy
+        self.backdoor_test = backdoor_test
+        if self.backdoor_test is not None:
+            self.backdoor_test.set_input_spec(self.net.input_spec)
         st = self.net.store
         self.w_global = st.data[0].clone()
         self.b_global = st.buffers[0].clone()
@@ -276,21 +282,28 @@ class FederatedBase:
         st = self.net.store
         self.mean(self.ctx, st.buffers[:G], coeffs, self.b_global)
 
-    @torch.no_grad()
     def test(self) -> float:
         """Server-model test accuracy in % (reference Server.test, hfl_complete.py:172-183)."""
-        if self.test_data is None:
+        return self._accuracy(self.test_data)
+
+    def test_backdoor(self) -> float:
+        """Server-model accuracy in % on ``backdoor_test``, the attack success rate (NaN without one)."""
+        return self._accuracy(self.backdoor_test)
+
+    @torch.no_grad()
+    def _accuracy(self, data) -> float:
+        if data is None or len(data) == 0:
             return float("nan")
         st = self.net.store
         self._download(1)
-        n = len(self.test_data) if self.eval_limit is None else min(self.eval_limit, len(self.test_data))
+        n = len(data) if self.eval_limit is None else min(self.eval_limit, len(data))
         correct = torch.zeros(1, dtype=torch.int64, device=self.dev)
         chunk = 2000
         with st.select(0, 1):
             for s in range(0, n, chunk):
                 e = min(n, s + chunk)
                 idx = torch.arange(s, e, dtype=torch.int32, device=self.dev).reshape(1, -1)
-                x, y = self.test_data.batch(idx)
+                x, y = data.batch(idx)
                 logits, _ = self.net.forward_native(x, False)
                 _, _, c = Fn.cross_entropy(logits, y, ncls=self.net.num_classes, want_grad=False,
                                            with_correct=True)
@@ -308,10 +321,10 @@ class FederatedBase:
             res.samples.append(samples)
             res.message_count.append(2 * self.round_idx * self.K)
             res.phase_ms.append(self.timer.summary())
-            if self.eval_every and self.round_idx % self.eval_every == 0:
-                res.test_accuracy.append(self.test())
-            else:
-                res.test_accuracy.append(float("nan"))
+            evaluate = self.eval_every and self.round_idx % self.eval_every == 0
+            res.test_accuracy.append(self.test() if evaluate else float("nan"))
+            if self.backdoor_test is not None:
+                res.backdoor_accuracy.append(self.test_backdoor() if evaluate else float("nan"))
         return res
 
 

@@ -8,12 +8,15 @@ reference README.md:89-92 / lab/README.md:13-16, has no code].
 * ``FreeRider``     — sends back the server weights unchanged (no local work).
 * ``ALIE`` / ``IPM`` — colluding model poisoning: every attacker sends the same vector, built from
                       the per-coordinate mean and std of other clients' updates (collude.hip).
+* ``Backdoor``      — the targeted attack: trigger-stamped, relabelled copies in the malicious
+                      clients' data, optionally boosted updates (model replacement).
 """
 from __future__ import annotations
 
 import math
 from statistics import NormalDist
 
+import numpy as np
 import torch
 
 from ..ops import functional as Fn
@@ -241,8 +244,83 @@ class IPM(Colluding):
         return self.eps
 
 
+class Backdoor(Attack):
+    """The targeted attack (Gu et al. 2017 BadNets; in FL Bagdasaryan et al. 2020): the malicious
+    clients train on copies of their own samples that carry a trigger, a ``patch`` x ``patch``
+    square of ``value`` in the bottom-right corner of every channel, labelled ``target``. The server
+    model keeps its accuracy on clean inputs and sends an input with the trigger to ``target``; the
+    accuracy on ``triggered_test`` is the attack success rate (ASR).
+
+    The poisoning is done on the host arrays before the device dataset is built (``poison``), so the
+    training step, its captured graph and the planners are those of a clean run, whatever the model,
+    precision or algorithm. ``boost`` != 1 is model replacement: a malicious row is sent as
+    ``w_g + boost * (w_k - w_g)``, to survive the average with the honest rows. No state."""
+
+    def __init__(self, malicious, target: int = 0, poison_fraction: float = 0.5, patch: int = 4,
+                 value: int = 255, boost: float = 1.0, seed: int = 0):
+        super().__init__(malicious)
+        self.target, self.patch, self.value = int(target), int(patch), int(value)
+        self.poison_fraction, self.boost, self.seed = float(poison_fraction), float(boost), int(seed)
+        if not 0.0 <= self.poison_fraction <= 1.0:
+            raise ValueError(f"poison_fraction must lie in [0, 1], got {poison_fraction}")
+        if self.patch < 1:
+            raise ValueError(f"patch must be >= 1, got {patch}")
+        if not 0 <= self.value <= 255:
+            raise ValueError(f"value must be a uint8 pixel, got {value}")
+        if self.target < 0:
+            raise ValueError(f"target must be a class index, got {target}")
+
+    def stamp(self, images: np.ndarray) -> np.ndarray:
+        """uint8 [n, H, W, C] -> a copy with the trigger in the bottom-right corner of every channel."""
+        out = np.array(images, dtype=np.uint8, copy=True)
+        out[:, -self.patch:, -self.patch:, :] = self.value
+        return out
+
+    def poison(self, arrays, client_indices):
+        """-> (arrays', client_indices'). For every malicious client m, round(poison_fraction * n_m)
+        of its samples with a label other than ``target`` (fewer when it has fewer), drawn with
+        ``default_rng([seed, 0xBD, m])``, are replaced in its index array by stamped copies labelled
+        ``target``, which are appended after the original rows. The first len(arrays) rows, the
+        benign clients' indices and every n_k stay. A pure function of the arguments: the ranks of a
+        distributed run build identical datasets."""
+        from ..data.images import ImageArrays
+        parts = [np.array(c, dtype=np.int64, copy=True) for c in client_indices]
+        images, nxt = [arrays.images], len(arrays)
+        for m in sorted(self.malicious):
+            if not 0 <= m < len(parts):
+                continue
+            idx = parts[m]
+            rng = np.random.default_rng([self.seed, 0xBD, m])
+            cand = np.flatnonzero(arrays.labels[idx] != self.target)
+            k = min(int(round(self.poison_fraction * len(idx))), len(cand))
+            pick = np.sort(rng.choice(cand, k, replace=False))  # positions in the client's index array
+            images.append(self.stamp(arrays.images[idx[pick]]))
+            idx[pick] = np.arange(nxt, nxt + k)
+            nxt += k
+        labels = np.concatenate([arrays.labels, np.full(nxt - len(arrays), self.target, dtype=arrays.labels.dtype)])
+        return ImageArrays(np.concatenate(images), labels, arrays.kind, arrays.synthetic), parts
+
+    def triggered_test(self, arrays):
+        """The samples whose true label is not ``target``, stamped and labelled ``target``."""
+        from ..data.images import ImageArrays
+        keep = arrays.labels != self.target
+        return ImageArrays(self.stamp(arrays.images[keep]),
+                           np.full(int(keep.sum()), self.target, dtype=arrays.labels.dtype),
+                           arrays.kind, arrays.synthetic)
+
+    def poison_updates(self, rows, w_global, slot_clients):
+        if self.boost == 1.0:
+            return
+        for i, c in enumerate(slot_clients):
+            if c in self.malicious:
+                if w_global is None:  # gradients without a centre: the row is the update
+                    rows[i].mul_(self.boost)
+                else:
+                    rows[i].sub_(w_global).mul_(self.boost).add_(w_global)
+
+
 def make_attack(name: str | None, malicious, **kw):
     if not name or name == "none":
         return None
     return {"label_flip": LabelFlip, "sign_flip": SignFlip, "gaussian": GaussianNoise,
-            "free_rider": FreeRider, "alie": ALIE, "ipm": IPM}[name](malicious, **kw)
+            "free_rider": FreeRider, "alie": ALIE, "ipm": IPM, "backdoor": Backdoor}[name](malicious, **kw)

@@ -41,7 +41,7 @@ def run_with_checkpoints(server, nr_rounds: int, path: str, every: int = 1) -> R
         res = RunResult(server.name, server.N, server.C, server.B, server.E, server.lr, server.seed)
     while server.round_idx < nr_rounds:
         part = server.run(1)
-        for f in ("wall_time", "round_time", "samples", "message_count", "test_accuracy"):
+        for f in ("wall_time", "round_time", "samples", "message_count", "test_accuracy", "backdoor_accuracy"):
             vals = getattr(part, f)
             if f == "wall_time" and getattr(res, f):
                 vals = [round(res.wall_time[-1] + v, 1) for v in vals]

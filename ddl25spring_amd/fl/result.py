@@ -24,12 +24,18 @@ class RunResult:
     round_time: list[float] = field(default_factory=list, repr=False)
     samples: list[int] = field(default_factory=list, repr=False)
     phase_ms: list[dict] = field(default_factory=list, repr=False)  # per-round device phase times
+    # accuracy on the triggered test set of a backdoor attack (the attack success rate), at the
+    # cadence of test_accuracy; empty unless the run was given one
+    backdoor_accuracy: list[float] = field(default_factory=list, repr=False)
 
     def as_df(self, skip_wtime: bool = True, with_throughput: bool = False):
         from pandas import DataFrame
         d = asdict(self)
         extra = {"round_time": d.pop("round_time"), "samples": d.pop("samples")}
         d.pop("phase_ms")
+        asr = d.pop("backdoor_accuracy")
+        if asr:  # a column of its own, only for a run that measured it
+            d["backdoor_accuracy"] = asr
         cols = {k.capitalize().replace("_", " "): v for k, v in d.items()}
         if cols["B"] == -1:
             cols["B"] = "\N{INFINITY}"

@@ -188,6 +188,8 @@ _SIGS = {
     "ddl_clip_scales": [vp, vp, i32, f64, vp, vp, vp],
     "ddl_gm_scales": [vp, vp, i32, f64, i32, vp, vp, vp, vp, vp],
     "ddl_clipped_sum": [vp, i64, vp, vp, i32, i64, vp, i32, vp],
+    "ddl_rlr_sum": [vp, i64, vp, vp, i32, i64, f32, vp, vp, vp],
+    "ddl_rlr_flip": [vp, vp, i64, f32, vp],
     "ddl_apply_update": [vp, vp, vp, i64, i64, f32, u64, u32, vp],
     "ddl_cc_step_blocks": [i64],
     "ddl_cc_step": [vp, i64, vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, vp],

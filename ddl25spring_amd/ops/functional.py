@@ -2057,6 +2057,59 @@ def clipped_sum(rows, center, cs, out, accumulate=False):
     return out
 
 
+def rlr_sum(rows, center, cs, delta, votes=None, theta=None):
+    """The clipped sum and the robust learning rate's sign vote (Ozdayi et al. 2021) in one read of
+    the rows (clip_agg.hip, ``ddl_rlr_sum``). Over the rows with cs[k] != 0 (the others are not read
+    and do not vote), with u_k = fl32(rows[k] - center) (the rows themselves without a centre):
+
+        delta[i] = sum_k cs[k] * u_ki     (``clipped_sum``'s order and roundings: the same bits)
+        s_i      = sum_k sgn(u_ki)        (sgn(+-0) = sgn(NaN) = 0; fp32, exact in any order)
+
+    ``theta`` None is the partial mode of several ranks: ``delta`` and ``votes`` (required) take
+    the sums as they are. ``theta >= 0`` is the final mode: delta[i] is negated where
+    |s_i| < theta, and ``votes`` is written when given. -> delta."""
+    G, n = rows.shape
+    if theta is None:
+        if votes is None:
+            raise ValueError("rlr_sum: the partial mode (theta=None) needs a votes buffer")
+    else:
+        theta = float(theta)
+        if not theta >= 0.0:
+            raise ValueError(f"rlr_sum: theta must be >= 0, got {theta}")
+    if G >= 1 << 24:
+        raise ValueError(f"rlr_sum: the fp32 vote counts hold fewer than 2^24 rows, got {G}")
+    if not rows.is_cuda:
+        ref.rlr_sum(rows, center, cs, delta, votes, theta)
+        return delta
+    assert rows.dtype == torch.float32 and (G == 0 or rows.stride(1) == 1)
+    for t in (delta,) + (() if votes is None else (votes,)) + (() if center is None else (center,)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == rows.device
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.numel() == G
+    if n:
+        check(_lib.kernels().ddl_rlr_sum(ptr(rows), rows.stride(0), ptr(center), ptr(cs), G, n,
+                                         -1.0 if theta is None else theta, ptr(delta), ptr(votes), stream()),
+              "rlr_sum")
+    return delta
+
+
+def rlr_flip(delta, votes, theta: float):
+    """delta[i] = -delta[i] where |votes[i]| < theta, in place (clip_agg.hip, ``ddl_rlr_flip``): the
+    second half of ``rlr_sum``'s partial mode, after the cross-rank sums of both vectors. -> delta."""
+    theta = float(theta)
+    if not theta >= 0.0:
+        raise ValueError(f"rlr_flip: theta must be >= 0, got {theta}")
+    if votes.numel() != delta.numel():
+        raise ValueError(f"rlr_flip: {votes.numel()} votes for {delta.numel()} coordinates")
+    if not delta.is_cuda:
+        ref.rlr_flip(delta, votes, theta)
+        return delta
+    for t in (delta, votes):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == delta.device
+    if delta.numel():
+        check(_lib.kernels().ddl_rlr_flip(ptr(delta), ptr(votes), delta.numel(), theta, stream()), "rlr_flip")
+    return delta
+
+
 def apply_update(out, center, delta, std: float = 0.0, seed: int = 0, round: int = 0, offset: int = 0):
     """out[j] = (center[j] or 0) + delta[j] + std * z[offset + j]; ``out`` may be ``center``.
 

@@ -485,6 +485,28 @@ def clipped_sum(rows, center, cs, out, accumulate=False):
     out.copy_(acc)
 
 
+def rlr_flip(delta, votes, theta):
+    th = torch.tensor(theta, dtype=torch.float32)  # the kernel compares in fp32
+    delta.copy_(torch.where(votes.abs() < th, -delta, delta))
+
+
+def rlr_sum(rows, center, cs, delta, votes=None, theta=None):
+    """rlr_sum_kernel's twin: clipped_sum's loop, the signs of the same differences counted beside it."""
+    acc = torch.zeros_like(delta)
+    s = torch.zeros_like(delta)
+    for k, c in enumerate(cs.tolist()):
+        if c == 0.0:
+            continue  # not read, no vote
+        d = rows[k] if center is None else rows[k] - center
+        acc = acc + cs[k] * d
+        s = s + ((d > 0).float() - (d < 0).float())  # both false for +-0 and NaN
+    delta.copy_(acc)
+    if theta is not None:
+        rlr_flip(delta, s, theta)
+    if votes is not None:
+        votes.copy_(s)
+
+
 def cc_step(rows, center, ctr_in, v_in, cs, v_out, ctr_out, want_norms=True):
     """cc_step_kernel's twin: the sum starts from v_in and adds the rows in order."""
     acc = v_in.clone()
