@@ -56,6 +56,12 @@ class LLMConfig:
     # "fp32": the reference's precision (fp32 activations, stage messages and math; deterministic
     # kernels) — the default; "bf16": bf16 activations / MFMA operands with fp32 master weights
     precision: str = "fp32"
+    # after training (dp = pp = tp = 1, fp32): continue the first ``sample_prompt_len`` tokens of a
+    # held-out batch by ``sample_tokens`` tokens (LLama.generate; 0: off). Temperature 0 is greedy.
+    sample_tokens: int = 0
+    sample_prompt_len: int = 8
+    sample_temperature: float = 0.0
+    sample_top_k: int = 0
 
 
 _RUN_FIELDS = ("vocab_size", "dmodel", "num_heads", "n_layers", "ctx_size", "batch_size",
@@ -75,6 +81,13 @@ def validate(cfg: "LLMConfig", world: int) -> None:
         raise ValueError(f"world {world} != dp {cfg.dp} x pp {cfg.pp} x tp {cfg.tp}")
     if cfg.batch_size % cfg.micro_batches:
         raise ValueError("batch_size must be divisible by micro_batches")
+    if cfg.sample_tokens:
+        if cfg.sample_tokens < 0 or cfg.dp > 1 or cfg.pp > 1 or cfg.tp > 1 or cfg.precision != "fp32":
+            raise ValueError(f"sample_tokens={cfg.sample_tokens} needs dp = pp = tp = 1 and precision='fp32': "
+                             "generation runs the whole fp32 model in one process")
+        if not 1 <= cfg.sample_prompt_len or cfg.sample_prompt_len + cfg.sample_tokens > cfg.ctx_size:
+            raise ValueError(f"sample_tokens: a prompt of {cfg.sample_prompt_len} + {cfg.sample_tokens} new tokens "
+                             f"does not fit ctx_size {cfg.ctx_size}")
     if cfg.tp > 1:
         if cfg.pp > 1:
             raise ValueError(f"tp={cfg.tp} with pp={cfg.pp}: tensor parallelism inside a pipeline is not supported")
@@ -280,6 +293,17 @@ def train_llm(cfg: LLMConfig, ctx, log=print, warmup: int = 0) -> dict:
     if ckpt is not None and (restored is None or restored[0] < total):
         save(total)
     tokens = cfg.dp * cfg.batch_size * cfg.ctx_size * timed
-    return {"losses": losses, "seconds": dt, "tokens_per_s": tokens / max(dt, 1e-9),
-            "ms_per_iter": 1e3 * dt / max(1, timed), "config": asdict(cfg),
-            "resumed_from": None if restored is None else restored[0]}
+    res = {"losses": losses, "seconds": dt, "tokens_per_s": tokens / max(dt, 1e-9),
+           "ms_per_iter": 1e3 * dt / max(1, timed), "config": asdict(cfg),
+           "resumed_from": None if restored is None else restored[0]}
+    if cfg.sample_tokens > 0:  # validate(): one process holds the whole fp32 model
+        prompt = next(stream)[:, :cfg.sample_prompt_len].to(dev)  # a batch the run has not trained on
+        samples = full.generate(prompt, max_new_tokens=cfg.sample_tokens, temperature=cfg.sample_temperature,
+                                top_k=cfg.sample_top_k, seed=cfg.seed).cpu()
+        res["samples"] = samples.tolist()  # [batch][sample_tokens] token ids (plain lists: the CLI prints JSON)
+        if log:
+            tok = SPTokenizer(cfg.vocab_size)
+            for b in range(samples.shape[0]):
+                log(f"sample {b}: prompt {prompt[b].tolist()} -> {samples[b].tolist()}")
+                log(f"sample {b}: {tok.decode(prompt[b].tolist())!r} -> {tok.decode(samples[b].tolist())!r}")
+    return res

@@ -166,6 +166,261 @@ class LLama(nn.Module):
     def forward(self, x):
         return self.last(self.first.embed(x))
 
+    # ------------------------------------------------------------------ generation (extension)
+    def blocks(self):
+        return list(self.first.layers) + list(self.last.layers)
+
+    def _check_generation(self):
+        if self.precision != "fp32":
+            raise NotImplementedError(f"generation runs the fp32 kernels only (precision={self.precision!r})")
+        if any(getattr(m, "tp", None) is not None for m in (self.first, self.last, *self.blocks())):
+            raise NotImplementedError("generation from a tensor-parallel (sharded) model is not supported")
+
+    @torch.no_grad()
+    def prefill(self, prompt_ids, prompt_lens, cache):
+        """Right-padded prompts [B, T] (real lengths ``prompt_lens`` [B]) through the blocks once:
+        every layer's K (rotated) and V go into ``cache``, ``cache.lens = prompt_lens``; returns
+        the logits of each sequence's last real position, [B, V] (``cache.logits``)."""
+        from ..ops import llama_decode as D
+        self._check_generation()
+        B, T = prompt_ids.shape
+        if B != cache.batch or T > cache.max_len:
+            raise ValueError(f"prefill: prompts {B} x {T} do not fit the cache ({cache.batch} x {cache.max_len})")
+        dev = cache.device
+        lens = torch.as_tensor(prompt_lens, dtype=torch.int32).to(dev)
+        x = A.embedding(prompt_ids.to(dev), self.first.emb, self.first.padding_idx, dtype=torch.float32)
+        for i, blk in enumerate(self.blocks()):
+            h, x = A.rmsnorm_fork(x, blk.norm1)
+            qkv = A.linear(h, blk.wqkv)
+            D.kv_append(qkv, cache.k(i), cache.v(i), cache.cos, cache.sin, 0)
+            x = A.linear(A.causal_attention(qkv, blk.h, blk.hd), blk.wo, residual=x)
+            h, x = A.rmsnorm_fork(x, blk.norm2)
+            x = A.linear(A.swiglu(A.linear(h, blk.w13)), blk.w2, residual=x)
+        last = x[torch.arange(B, device=dev), (lens - 1).long()].contiguous()  # [B, D], no host sync
+        if B <= D.LIN_ROWS_MAX_T:
+            D.lin_rows(last, self.last.head.detach(), cache.logits, pro="rmsnorm", gain=self.last.norm.detach())
+        else:
+            cache.logits.copy_(A.linear(A.rmsnorm(last, self.last.norm), self.last.head))
+        cache.lens.copy_(lens)
+        cache.finished.zero_()
+        cache.step.zero_()
+        return cache.logits
+
+    @torch.no_grad()
+    def decode_step(self, cache, tokens=None, fused: bool = True, advance=None):
+        """One token per sequence through the cached model: ``tokens`` [B] (forced decoding) or
+        ``cache.next_tok``. Launches: the embedding; per layer norm+qkv, attention with the cache
+        append, wo+residual, norm+w13, swiglu+w2+residual; norm+head. ``fused=False`` runs the
+        existing rmsnorm / swiglu kernels before plain skinny linears (A/B and cross-check).
+        Returns the static [B, V] logits buffer. ``advance`` (default: when ``tokens`` are given)
+        adds the appended row to ``cache.lens`` here; in ``generate`` the sampler does."""
+        from ..ops import llama_decode as D
+        self._check_generation()
+        c = cache
+        if tokens is not None:
+            if not tokens.is_cuda and (int(tokens.min()) < 0 or int(tokens.max()) >= self.first.vocab_size):
+                raise ValueError(f"decode_step: token outside [0, {self.first.vocab_size})")
+            c.next_tok.copy_(tokens.to(torch.int32))
+        c.embed(self.first.emb.detach())
+        if c.batch > D.LIN_ROWS_MAX_T:
+            self._decode_wide(c)
+        else:
+            xa, xb = c.xa, c.xb
+            for i, blk in enumerate(self.blocks()):
+                n1, n2 = blk.norm1.detach(), blk.norm2.detach()
+                if fused:
+                    D.lin_rows(xa, blk.wqkv.detach(), c.qkv, pro="rmsnorm", gain=n1)
+                else:
+                    D.lin_rows(c.rmsnorm(xa, n1), blk.wqkv.detach(), c.qkv)
+                D.attn_decode(c.qkv, c.k(i), c.v(i), c.lens, c.cos, c.sin, c.att, c.splits, c.ws)
+                D.lin_rows(c.att, blk.wo.detach(), xb, residual=xa)
+                if fused:
+                    D.lin_rows(xb, blk.w13.detach(), c.h13, pro="rmsnorm", gain=n2)
+                    D.lin_rows(c.h13, blk.w2.detach(), xa, residual=xb, pro="swiglu")
+                else:
+                    D.lin_rows(c.rmsnorm(xb, n2), blk.w13.detach(), c.h13)
+                    D.lin_rows(c.swiglu(c.h13), blk.w2.detach(), xa, residual=xb)
+            if fused:
+                D.lin_rows(xa, self.last.head.detach(), c.logits, pro="rmsnorm", gain=self.last.norm.detach())
+            else:
+                D.lin_rows(c.rmsnorm(xa, self.last.norm.detach()), self.last.head.detach(), c.logits)
+        if tokens is not None if advance is None else advance:
+            c.lens.add_((c.lens < c.max_len).to(torch.int32))
+        return c.logits
+
+    def _decode_wide(self, c):
+        """More than 16 sequences: the linears on the training engine (``A.linear``); the decode
+        attention and the sampler have no such limit."""
+        from ..ops import llama_decode as D
+        x = c.xa
+        for i, blk in enumerate(self.blocks()):
+            c.qkv.copy_(A.linear(A.rmsnorm(x, blk.norm1), blk.wqkv))
+            D.attn_decode(c.qkv, c.k(i), c.v(i), c.lens, c.cos, c.sin, c.att, c.splits, c.ws)
+            x = A.linear(c.att, blk.wo, residual=x)
+            x = A.linear(A.swiglu(A.linear(A.rmsnorm(x, blk.norm2), blk.w13)), blk.w2, residual=x)
+        c.logits.copy_(A.linear(A.rmsnorm(x, self.last.norm), self.last.head))
+
+    @torch.no_grad()
+    def generate(self, prompt_ids, prompt_lens=None, max_new_tokens: int = 32, temperature: float = 0.0,
+                 top_k: int = 0, seed: int = 0, eos_id=None, graph=None, fused=None, return_logits: bool = False,
+                 cache=None):
+        """Continue right-padded prompts [B, T] by ``max_new_tokens`` tokens -> int64 [B, N]
+        (``return_logits``: also the fp32 [B, N, V] logits each token was drawn from).
+        ``temperature == 0`` is greedy; else temperature / ``top_k`` sampling, a pure function of
+        ``seed``. After ``eos_id`` a sequence emits ``eos_id``. One prefill, then N - 1 cached
+        steps whose state (token, lengths, finished flags, Philox counter) stays on the device:
+        the loop never waits for the GPU, and with ``graph`` every step is one HIP-graph replay.
+        ``cache``: a ``KVCache`` to reuse (its captured step included). Unset ``graph`` /
+        ``fused`` take ``GENERATE_DEFAULTS``."""
+        from ..ops import llama_decode as D
+        self._check_generation()
+        if prompt_ids.dim() != 2 or prompt_ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError("generate: prompt_ids must be an integer tensor [B, T]")
+        B, T = prompt_ids.shape
+        N = int(max_new_tokens)
+        V = self.first.vocab_size
+        if prompt_lens is None:
+            plens = [T] * B
+        else:
+            plens = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+        if len(plens) != B or min(plens) < 1 or max(plens) > T:
+            raise ValueError(f"generate: prompt_lens {plens} for prompts of shape {B} x {T}")
+        if N < 1:
+            raise ValueError("generate: max_new_tokens must be at least 1")
+        ctx = self.first.ctx_size
+        if max(plens) + N > ctx:
+            raise ValueError(f"generate: prompt of {max(plens)} + {N} new tokens exceeds ctx_size {ctx}")
+        lo, hi = (int(prompt_ids.min()), int(prompt_ids.max())) if not prompt_ids.is_cuda else \
+            torch.stack([prompt_ids.min(), prompt_ids.max()]).tolist()  # the one read before the loop
+        if lo < 0 or hi >= V:
+            raise ValueError(f"generate: prompt token outside [0, {V})")
+        eos = -1 if eos_id is None else int(eos_id)
+        if eos >= V:
+            raise ValueError(f"generate: eos_id {eos} outside the vocabulary")
+        need = max(plens) + N
+        if cache is None:
+            cache = KVCache(self, B, need)
+        elif cache.batch != B or cache.max_len < need:
+            raise ValueError(f"generate: the cache ({cache.batch} x {cache.max_len}) does not fit {B} x {need}")
+        dev = cache.device
+        on_gpu = dev.type == "cuda"
+        fused = GENERATE_DEFAULTS["fused"] if fused is None else bool(fused)
+        graph = (GENERATE_DEFAULTS["graph"] if graph is None else bool(graph)) and on_gpu \
+            and B <= D.LIN_ROWS_MAX_T
+        out = torch.zeros(B, N, dtype=torch.int32, device=dev)
+        cache.out = out
+
+        def one_step():
+            self.decode_step(cache, fused=fused)
+            D.sample(cache.logits, cache.next_tok, cache.out, cache.lens, cache.finished, cache.step,
+                     cache.max_len, temperature, top_k, seed, eos, advance=True)
+
+        step = one_step
+        if graph:  # a captured step writes the token buffer it was recorded with, kept beside the graph
+            step = cache.captured_step((float(temperature), int(top_k), int(seed), eos, fused, N), one_step, N)
+            out = cache.out
+            out.zero_()
+        logits = self.prefill(prompt_ids, plens, cache)
+        all_logits = torch.empty(B, N, V, dtype=torch.float32, device=dev) if return_logits else None
+        if return_logits:
+            all_logits[:, 0].copy_(logits)
+        D.sample(logits, cache.next_tok, out, cache.lens, cache.finished, cache.step, cache.max_len, temperature,
+                 top_k, seed, eos, advance=False)
+        for i in range(1, N):
+            step()
+            if return_logits:
+                all_logits[:, i].copy_(cache.logits)
+        toks = out.long()
+        return (toks, all_logits) if return_logits else toks
+
+
+# ``generate``'s defaults, as measured by benchmarks/bench_generate.py (profiles/generate.txt): the graph
+# replay is 1.9x the eager loop at B = 1 and level with it at B = 16, the fused prologues 6-14 % ahead
+GENERATE_DEFAULTS = {"graph": True, "fused": True}
+
+
+class KVCache:
+    """Everything a decode step reads or writes, allocated once: one fp32 buffer
+    [layers][2][B][H][max_len][hd] (K stored rotated), the device-side sequence state (``lens``,
+    ``finished``, ``next_tok``, the per-row step counter ``step``; int32 [B]), RoPE tables of
+    ``max_len`` rows and the step's activation buffers."""
+
+    def __init__(self, model: "LLama", batch: int, max_len: int):
+        from ..ops import llama_decode as D
+        from ..ops.autograd_ops import rope_tables
+        model._check_generation()
+        if max_len < 1 or max_len > model.first.ctx_size:
+            raise ValueError(f"KVCache: max_len {max_len} outside [1, ctx_size = {model.first.ctx_size}]")
+        if batch < 1:
+            raise ValueError("KVCache: batch must be at least 1")
+        blocks = model.blocks()
+        dev = model.first.emb.device
+        H, hd, Dm, V = blocks[0].h, blocks[0].hd, model.first.dmodel, model.first.vocab_size
+        F = blocks[0].w2.shape[1]
+        self.batch, self.max_len, self.device = batch, max_len, dev
+        self.kv = torch.zeros(len(blocks), 2, batch, H, max_len, hd, dtype=torch.float32, device=dev)
+
+        def ibuf():
+            return torch.zeros(batch, dtype=torch.int32, device=dev)
+
+        def fbuf(n):
+            return torch.zeros(batch, n, dtype=torch.float32, device=dev)
+
+        self.lens, self.finished, self.next_tok, self.step = ibuf(), ibuf(), ibuf(), ibuf()
+        self.cos, self.sin = rope_tables(max_len, hd, dev)
+        self.xa, self.xb, self.xn, self.att = fbuf(Dm), fbuf(Dm), fbuf(Dm), fbuf(Dm)
+        self.qkv, self.h13, self.hh, self.logits = fbuf(3 * Dm), fbuf(2 * F), fbuf(F), fbuf(V)
+        self.rstd = torch.zeros(batch, dtype=torch.float32, device=dev)
+        self.splits = D.attn_splits(max_len)
+        self.ws = D.attn_workspace(batch, H, hd, self.splits, dev)
+        self.out = None
+        self._graphs: dict = {}
+
+    def k(self, layer: int):
+        return self.kv[layer, 0]
+
+    def v(self, layer: int):
+        return self.kv[layer, 1]
+
+    # the step's launches that are not in ops/llama_decode.py: existing kernels on static buffers
+    def embed(self, emb):
+        if not emb.is_cuda:
+            self.xa.copy_(emb[self.next_tok.long()])
+            return
+        from ..ops import llama_f32 as L32
+        L32.check(L32.K().ddl_embf_fwd(L32.ptr(self.next_tok), L32.ptr(emb), L32.ptr(self.xa), self.batch,
+                                       emb.shape[1], L32.stream()), "embf_fwd")
+
+    def rmsnorm(self, x, g, eps=1e-6):
+        if not x.is_cuda:
+            self.xn.copy_(A.rmsnorm(x, g, eps))
+            return self.xn
+        from ..ops import llama_f32 as L32
+        L32.check(L32.K().ddl_rmsf_fwd(L32.ptr(x), L32.ptr(g), L32.ptr(self.xn), L32.ptr(self.rstd), self.batch,
+                                       x.shape[1], float(eps), L32.stream()), "rmsf_fwd")
+        return self.xn
+
+    def swiglu(self, ab):
+        if not ab.is_cuda:
+            self.hh.copy_(A.swiglu(ab))
+            return self.hh
+        from ..ops import llama_f32 as L32
+        L32.check(L32.K().ddl_swiglu_f32_fwd(L32.ptr(ab), L32.ptr(self.hh), self.batch, self.hh.shape[1],
+                                             L32.stream()), "swiglu_f32_fwd")
+        return self.hh
+
+    def captured_step(self, key, fn, n_out: int):
+        """The HIP-graph replay of ``fn`` for these sampling parameters (single stream, no parallel
+        branches), kept with the cache so a later ``generate`` replays without capturing again. The
+        graph writes the cache's own token buffer ``self.out``."""
+        from ..runtime.graphs import CapturedStep
+        ent = self._graphs.get(key)
+        if ent is None:
+            ent = (CapturedStep(fn), torch.zeros(self.batch, n_out, dtype=torch.int32, device=self.device))
+            self._graphs[key] = ent
+        self.out = ent[1]
+        return ent[0]
+
 
 def split_stages(model: LLama, n_stages: int):
     """Cut a whole LLama into n_stages modules sharing its parameters (first / middle / last)."""
