@@ -1,7 +1,7 @@
 """Command-line entry point: ``python -m ddl25spring_amd <program> [--field value ...]``.
 
 Programs: fl (horizontal FL), vfl (centralized / split-NN / VAE / VFL-VAE on heart-disease),
-gan (federated DCGAN), llm (LLaMA DP x PP). Every dataclass field of the program's config is a
+gan (federated DCGAN), llm (LLaMA DP x PP), fedlora (federated LoRA fine-tuning of the LLaMA). Every dataclass field of the program's config is a
 flag (``--client-fraction 0.1``, ``--iid false``). Multi-rank: start under
 ``python -m ddl25spring_amd.runtime.launch -n W`` or torchrun (env rendezvous on 127.0.0.1);
 rank r uses GPU r, RCCL between GPUs, gloo on CPU.
@@ -38,6 +38,7 @@ PROGRAMS = {
     "vfl": ("apps.vfl", "VFLConfig", "run_vfl"),
     "gan": ("apps.gan", "GANConfig", "run_gan"),
     "llm": ("apps.llm", "LLMConfig", "train_llm"),
+    "fedlora": ("apps.fedlora", "FedLoRAConfig", "run_fedlora"),
 }
 
 

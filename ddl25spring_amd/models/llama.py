@@ -54,15 +54,32 @@ class Block(nn.Module):
             self.wo.mul_(1 / math.sqrt(2))
             self.w2.mul_(1 / math.sqrt(2))
 
+    # low-rank adapters of the targeted linears (models/lora.py: attach_lora); None = the plain block
+    lora = None
+
     def forward(self, x):  # x [B, S, D]
         if self.tp is not None:
             return self.forward_tp(x)
+        if self.lora is not None and self.lora.active:
+            return self.forward_lora(x)
         h, x = A.rmsnorm_fork(x, self.norm1)
         qkv = A.linear(h, self.wqkv)
         att = A.causal_attention(qkv, self.h, self.hd)
         x = A.linear(att, self.wo, residual=x)
         h, x = A.rmsnorm_fork(x, self.norm2)
         return A.linear(A.swiglu(A.linear(h, self.w13)), self.w2, residual=x)
+
+    def forward_lora(self, x):
+        """The block on a frozen base with per-slot adapters: x [S b, ctx, D] is slot-major, and each
+        targeted linear's output gets scale (x A_s^T) B_s^T of its slot added in place."""
+        lo = self.lora
+        h, x = A.rmsnorm_fork(x, self.norm1)
+        qkv = lo.add("wqkv", A.linear(h, self.wqkv), h)
+        att = A.causal_attention(qkv, self.h, self.hd)
+        x = lo.add("wo", A.linear(att, self.wo, residual=x), att)
+        h, x = A.rmsnorm_fork(x, self.norm2)
+        g = A.swiglu(lo.add("w13", A.linear(h, self.w13), h))
+        return lo.add("w2", A.linear(g, self.w2, residual=x), g)
 
     def forward_tp(self, x):
         """The sharded block: wqkv / w13 hold this rank's heads / SwiGLU columns (column-parallel,
@@ -162,6 +179,8 @@ class LLama(nn.Module):
                                    precision)
         if device is not None:
             self.to(device)
+
+    lora = None  # the model's LoRAAdapters once models/lora.py: attach_lora has run
 
     def forward(self, x):
         return self.last(self.first.embed(x))

@@ -295,6 +295,17 @@ class SlotAdam:
         self.grad.zero_()
 
     @torch.no_grad()
+    def reset_state(self, rows: int | None = None):
+        """Forget the first ``rows`` slots' moments and step counts (clients that are stateless
+        between rounds start every round as a fresh Adam)."""
+        r = self.S if rows is None else rows
+        self.m[:r].zero_()
+        self.v[:r].zero_()
+        self.t[:r] = [0] * r
+        if self.t_dev is not None:
+            self.t_dev[:r].zero_()
+
+    @torch.no_grad()
     def step(self, rows: int | None = None):
         r = self.S if rows is None else rows
         for i in range(r):
