@@ -14,6 +14,13 @@ them alike. Times are host clocks around work that ends in a device synchronise.
     lin_rows at the model's five decode shapes against one read of its weight bytes at the 8 TB/s
     HBM specification, decode attention at L = 255 for B in {1, 16}, the sampler at V = 32000;
   * launches per step, counted from the chain the step runs.
+
+``--adapters R`` measures per-sequence LoRA adapters instead (``generate(adapters=, adapter_ids=)``,
+rank 8 on all four targets): the base step against the adapter step at each B with mixed ids, 16
+personalised continuations in one call against 16 x (merge, generate at B = 1, unmerge), the two
+adapter kernels at the model's shapes, and the step's overhead against its 24 extra launches.
+
+    python benchmarks/bench_generate.py --adapters 8 --out profiles/adapter_generate.txt
 """
 from __future__ import annotations
 
@@ -153,6 +160,97 @@ def bench_kernels(model, lines):
                  f"unfused {1 + 8 * n + 2 + 1}")
 
 
+def _spread(ts, new):
+    return f"{1e6 * statistics.median(ts) / new:8.1f} us/step (min {1e6 * min(ts) / new:.1f}, max {1e6 * max(ts) / new:.1f})"
+
+
+def bench_adapters(model, R, batches, prompt, new, reps, lines):
+    """Per-sequence LoRA adapters (rank 8, all four targets, R adapters, mixed ids with base rows):
+    the base step against the adapter step per B, then 16 personalised continuations in one
+    ``generate`` against the route without per-sequence adapters (16 x merge, B = 1, unmerge), the
+    adapter kernels alone, and the step's overhead against its extra launches."""
+    from ddl25spring_amd.models.lora import LoRAConfig, adapter_bank, attach_lora, merge_lora, unmerge_lora
+    dev = torch.device("cuda")
+    ad = attach_lora(model, R, LoRAConfig(rank=8, alpha=16.0), seed=0)
+    rows = ad.make_optimizer().data
+    g = torch.Generator().manual_seed(1)
+    rows.copy_((torch.randn(rows.shape, generator=g) * 0.02).to(dev))
+    bank = adapter_bank(model, rows)
+    n_layers, n_t = len(model.blocks()), len(bank.targets)
+    base_l, extra_l = 1 + 5 * n_layers + 2, n_t * n_layers
+    lines.append(f"adapters: R = {R}, rank {bank.rank}, targets {','.join(bank.targets)}; launches per step: base "
+                 f"{base_l}, with adapters {base_l + extra_l} (one shrink per adapted linear; the expand is fused)")
+    torch.manual_seed(1)
+    step_us = {}
+    for B in batches:
+        ids = torch.randint(0, model.first.vocab_size, (B, prompt), device=dev)
+        aids = [(b % (R + 1)) - 1 for b in range(B)] if B > 1 else [0]
+        caches = {v: KVCache(model, B, prompt + new) for v in ("base", "adapters")}
+        times = {v: [] for v in caches}
+        for rep in range(reps + 1):  # repeat 0 warms up and captures
+            for v in caches:
+                kw = dict(adapters=bank, adapter_ids=aids) if v == "adapters" else {}
+                dt = _sync_time(lambda: model.generate(ids, max_new_tokens=new, cache=caches[v], **kw))
+                if rep:
+                    times[v].append(dt)
+        for v in caches:
+            lines.append(f"generate B={B:2d} {v:8s}: {B * new / statistics.median(times[v]):9.0f} tok/s  "
+                         f"{_spread(times[v], new)}  (graph, fused, prefill included; of {reps})")
+        step_us[B] = tuple(1e6 * statistics.median(times[v]) / new for v in ("base", "adapters"))
+    # ---- 16 personalised continuations
+    B = 16
+    ids = torch.randint(0, model.first.vocab_size, (B, prompt), device=dev)
+    aids = [b % R for b in range(B)]
+    c16, c1 = KVCache(model, B, prompt + new), KVCache(model, 1, prompt + new)
+
+    def merged_route():
+        for b in range(B):
+            merge_lora(model, rows[aids[b]])
+            model.generate(ids[b:b + 1], max_new_tokens=new, cache=c1)
+            unmerge_lora(model)
+
+    ta, tm = [], []
+    for rep in range(reps + 1):
+        a = _sync_time(lambda: model.generate(ids, max_new_tokens=new, cache=c16, adapters=bank, adapter_ids=aids))
+        m = _sync_time(merged_route)
+        if rep:
+            ta.append(a)
+            tm.append(m)
+    ma, mm = statistics.median(ta), statistics.median(tm)
+    lines.append(f"16 personalised continuations of {new} tokens: one generate with adapter ids {1e3 * ma:8.1f} ms "
+                 f"(min {1e3 * min(ta):.1f}, max {1e3 * max(ta):.1f}); 16 x (merge_lora, generate B=1, unmerge_lora) "
+                 f"{1e3 * mm:8.1f} ms (min {1e3 * min(tm):.1f}, max {1e3 * max(tm):.1f}); ratio {mm / ma:.1f}x")
+    # ---- the kernels alone (graph replays of 50 launches)
+    blk = model.blocks()[0]
+    shapes = [("norm+qkv", "wqkv", blk.wqkv, "rmsnorm", blk.norm1, False), ("wo+res", "wo", blk.wo, "none", None, True),
+              ("norm+w13", "w13", blk.w13, "rmsnorm", blk.norm2, False),
+              ("swiglu+w2+res", "w2", blk.w2, "swiglu", None, True)]
+    for B in (1, 16):
+        aid = torch.tensor([b % R for b in range(B)], dtype=torch.int32, device=dev)
+        none = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        u = torch.zeros(B, bank.rank, device=dev)
+        for name, t, w, pro, gain, res in shapes:
+            w = w.detach()
+            Kout, C = w.shape
+            x = torch.randn(B, 2 * C if pro == "swiglu" else C, device=dev)
+            out, r = torch.empty(B, Kout, device=dev), torch.randn(B, Kout, device=dev)
+            gn = None if gain is None else gain.detach()
+            pa, pb = bank.pair(0, t)
+            t_plain = _graph_time(lambda: D.lin_rows(x, w, out, r if res else None, pro, gn))
+            t_lora = _graph_time(lambda: D.lin_rows(x, w, out, r if res else None, pro, gn,
+                                                    lora=(u, pb, aid, bank.scale)))
+            t_u = _graph_time(lambda: D.lora_rows_u(x, pa, aid, u, pro, gn))
+            lines.append(f"{name:14s} T={B:2d} C={C:4d} K={Kout:5d}: lin_rows {1e6 * t_plain:6.2f} us, with the fused "
+                         f"expand {1e6 * t_lora:6.2f} us, lora_rows_u {1e6 * t_u:6.2f} us")
+        x = torch.randn(B, blk.wo.shape[1], device=dev)
+        t_none = _graph_time(lambda: D.lora_rows_u(x, bank.pair(0, "wo")[0], none, u))
+        t_launch = _graph_time(lambda: u.zero_())
+        base_us, ad_us = step_us.get(B, (float("nan"),) * 2)
+        lines.append(f"per launch T={B:2d}: {1e6 * t_launch:5.2f} us (a fill of u's {u.numel()} floats; lora_rows_u with every "
+                     f"id -1: {1e6 * t_none:5.2f} us); the step's {extra_l} extra launches: {1e6 * extra_l * t_launch:6.1f} us; "
+                     f"measured step overhead {ad_us - base_us:6.1f} us ({ad_us:.1f} - {base_us:.1f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -161,6 +259,8 @@ def main():
     ap.add_argument("--new", type=int, default=224)
     ap.add_argument("--baseline-new", type=int, default=64)
     ap.add_argument("--batches", default="1,8,16")
+    ap.add_argument("--adapters", type=int, default=0,
+                    help="R > 0: time generation with R per-sequence LoRA adapters instead (profiles/adapter_generate.txt)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate measures the GPU path: no GPU found")
@@ -168,10 +268,14 @@ def main():
     model = LLama(device="cuda")
     lines = [f"bench_generate: LLama 288d / 6 layers / 6 heads / V 32000 / ctx 256, fp32, random init; prompt "
              f"{args.prompt}, {args.new} new tokens, greedy; medians of {args.reps} (variants alternated per repeat)"]
-    for B in (int(b) for b in args.batches.split(",")):
-        bench_generate(model, B, args.prompt, args.new, args.reps, lines)
-    bench_baseline(model, args.prompt, args.baseline_new, max(3, args.reps // 2), lines)
-    bench_kernels(model, lines)
+    batches = [int(b) for b in args.batches.split(",")]
+    if args.adapters > 0:
+        bench_adapters(model, args.adapters, batches, args.prompt, args.new, args.reps, lines)
+    else:
+        for B in batches:
+            bench_generate(model, B, args.prompt, args.new, args.reps, lines)
+        bench_baseline(model, args.prompt, args.baseline_new, max(3, args.reps // 2), lines)
+        bench_kernels(model, lines)
     text = "\n".join(lines)
     print(text, flush=True)
     if args.out:

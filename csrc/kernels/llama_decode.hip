@@ -7,6 +7,9 @@
 //                        wave per output column (four on wide outputs), x staged once per workgroup
 //                        in LDS with the prologue applied while staging (none | rmsnorm | swiglu),
 //                        an fmaf chain per lane and one xor-butterfly wave reduction
+//   ddl_lora_rows_u      per-sequence adapters (row t uses adapter ids[t]; an id out of range = none):
+//   ddl_lin_rows_lora_f32  the shrink u = pro(x) A[ids[t]]^T on the rows lin_rows stages, one workgroup
+//                        per row; the expand y += scale u B[ids[t]]^T in lin_rows' own epilogue
 //   ddl_attnf_decode     single-query attention over one layer's cache [B][H][Smax][HD] (K stored
 //                        rotated) with the step's K / V row appended by split 0 of the same launch;
 //                        grid (H, B, NS), NS fixed from Smax on the host so the launch is capturable;
@@ -81,15 +84,13 @@ __device__ __forceinline__ float dec_w(float m, float nm) { return m == -INFINIT
 constexpr int LR_MAX_T = 16, LR_LDS_BYTES = 65536, LR_RMS_MAXV = 8;
 enum { LR_NONE = 0, LR_RMS = 1, LR_SWIGLU = 2 };
 
-template <int TT, int R>
-__global__ __launch_bounds__(256) void lin_rows_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                           const float* __restrict__ res,
-                                                           const float* __restrict__ gain, float* __restrict__ y,
-                                                           int T, int C, int K, int pro, float eps) {
-  extern __shared__ __attribute__((aligned(16))) float lr_xs[];  // [TT][C]
+// pro(x) rows 0 .. TT - 1 into LDS (rows >= T zero), by the whole workgroup; x rows are xs floats
+// apart. The one staging routine of every kernel here that reads pro(x): their staged bits agree.
+template <int TT>
+__device__ __forceinline__ void lr_stage(const float* __restrict__ x, const float* __restrict__ gain, float4* xs4,
+                                         int T, int C, int pro, float eps) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int C4 = C / 4;
-  float4* xs4 = (float4*)lr_xs;
   if (pro == LR_RMS) {
     // a wave per row, as ddl_rmsf_fwd: the lane's slices in registers, the same sums and products
     for (int t = wv; t < TT; t += 4) {
@@ -131,6 +132,50 @@ __global__ __launch_bounds__(256) void lin_rows_f32_kernel(const float* __restri
       xs4[e] = v;
     }
   }
+}
+
+// The adapters of a decode step (multi-LoRA serving: row t of the batch uses adapter ids[t]).
+// u [T][r] = pro(x) A[ids[t]]^T comes from ddl_lora_rows_u; B [Rn][K][r], slots bs floats apart.
+// An id outside [0, Rn) means "no adapter": no index is formed from it.
+struct LrLora {
+  const float* u;
+  const float* B;
+  const int* ids;
+  long long bs;
+  int Rn, r;
+  float scale;
+};
+
+// the LoRA term of output (t, k): an fmaf chain over j ascending from 0
+__device__ __forceinline__ float lr_delta(const LrLora& lo, int id, int t, int k) {
+  const float4* u4 = (const float4*)(lo.u + (long long)t * lo.r);
+  const float4* b4 = (const float4*)(lo.B + (long long)id * lo.bs + (long long)k * lo.r);
+  float d = 0.f;
+  for (int j = 0; j < lo.r / 4; ++j) {
+    const float4 uv = u4[j], bv = b4[j];
+    d = fmaf(uv.x, bv.x, d);
+    d = fmaf(uv.y, bv.y, d);
+    d = fmaf(uv.z, bv.z, d);
+    d = fmaf(uv.w, bv.w, d);
+  }
+  return d;
+}
+
+template <int TT, int R, bool LORA>
+__global__ __launch_bounds__(256) void lin_rows_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ res,
+                                                           const float* __restrict__ gain, float* __restrict__ y,
+                                                           int T, int C, int K, int pro, float eps, LrLora lo) {
+  extern __shared__ __attribute__((aligned(16))) float lr_xs[];  // [TT][C]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int C4 = C / 4;
+  float4* xs4 = (float4*)lr_xs;
+  int id = -1;  // lane t owns row t's outputs: its adapter, read ahead of the W stream
+  if (LORA && lane < T) {
+    id = lo.ids[lane];
+    if (id < 0 || id >= lo.Rn) id = -1;
+  }
+  lr_stage<TT>(x, gain, xs4, T, C, pro, eps);
   __syncthreads();
   const int k0 = (blockIdx.x * 4 + wv) * R;
   if (k0 >= K) return;
@@ -158,6 +203,26 @@ __global__ __launch_bounds__(256) void lin_rows_f32_kernel(const float* __restri
       }
     }
   }
+  if (LORA) {
+    // every lane keeps its own row's sums, then the T owning lanes run their epilogues side by side:
+    // one round of u / B / residual loads for the wave, not one per row
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float mine = 0.f;
+#pragma unroll
+      for (int t = 0; t < TT; ++t) {
+        const float s = wave_sum(acc[r][t]);
+        if (lane == t) mine = s;
+      }
+      const int k = k0 + r;
+      if (lane < T && k < K) {
+        const long long at = (long long)lane * K + k;
+        if (id >= 0) mine = fmaf(lo.scale, lr_delta(lo, id, lane, k), mine);  // no adapter: the sum as it is
+        y[at] = res ? mine + res[at] : mine;
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
 #pragma unroll
@@ -172,33 +237,124 @@ __global__ __launch_bounds__(256) void lin_rows_f32_kernel(const float* __restri
   }
 }
 
-template <int TT>
+template <int TT, bool LORA>
 static int lin_rows_launch(const float* x, const float* w, const float* res, const float* gain, float* y, int T,
-                           int C, int K, int pro, float eps, hipStream_t s) {
+                           int C, int K, int pro, float eps, const LrLora& lo, hipStream_t s) {
   const size_t lds = (size_t)TT * C * sizeof(float);
   if (lds > (size_t)LR_LDS_BYTES) return (int)hipErrorInvalidValue;
   if (K > 4096) {  // wide outputs (the LM head): four columns per wave, four W rows in flight per lane
-    hipLaunchKernelGGL((lin_rows_f32_kernel<TT, 4>), dim3((K + 15) / 16), dim3(256), lds, s, x, w, res, gain, y, T,
-                       C, K, pro, eps);
+    hipLaunchKernelGGL((lin_rows_f32_kernel<TT, 4, LORA>), dim3((K + 15) / 16), dim3(256), lds, s, x, w, res, gain, y,
+                       T, C, K, pro, eps, lo);
   } else {
-    hipLaunchKernelGGL((lin_rows_f32_kernel<TT, 1>), dim3((K + 3) / 4), dim3(256), lds, s, x, w, res, gain, y, T,
-                       C, K, pro, eps);
+    hipLaunchKernelGGL((lin_rows_f32_kernel<TT, 1, LORA>), dim3((K + 3) / 4), dim3(256), lds, s, x, w, res, gain, y,
+                       T, C, K, pro, eps, lo);
   }
   return (int)hipGetLastError();
+}
+
+static bool lin_rows_args_ok(const float* x, const float* w, const float* gain, const float* y, int T, int C, int K,
+                             int pro) {
+  if (!x || !w || !y || T < 1 || T > LR_MAX_T || C < 4 || C % 4 || K < 1) return false;
+  if (pro != LR_NONE && pro != LR_RMS && pro != LR_SWIGLU) return false;
+  if (pro == LR_RMS && (!gain || C > 256 * LR_RMS_MAXV)) return false;
+  return true;
+}
+
+template <bool LORA>
+static int lin_rows_dispatch(const float* x, const float* w, const float* res, const float* gain, float* y, int T,
+                             int C, int K, int pro, float eps, const LrLora& lo, hipStream_t s) {
+  if (T == 1) return lin_rows_launch<1, LORA>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
+  if (T == 2) return lin_rows_launch<2, LORA>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
+  if (T <= 4) return lin_rows_launch<4, LORA>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
+  if (T <= 8) return lin_rows_launch<8, LORA>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
+  return lin_rows_launch<16, LORA>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
 }
 
 // x [T][C] ([T][2C] = [a | b] for the swiglu prologue), w [K][C], res / y [T][K]; gain [C] for the
 // rmsnorm prologue (C <= 2048 there, as ddl_rmsf_fwd). The staged rows must fit 64 KB of LDS.
 DDL_API int ddl_lin_rows_f32(const float* x, const float* w, const float* res, const float* gain, float* y, int T,
                              int C, int K, int pro, float eps, hipStream_t s) {
-  if (!x || !w || !y || T < 1 || T > LR_MAX_T || C < 4 || C % 4 || K < 1) return (int)hipErrorInvalidValue;
-  if (pro != LR_NONE && pro != LR_RMS && pro != LR_SWIGLU) return (int)hipErrorInvalidValue;
-  if (pro == LR_RMS && (!gain || C > 256 * LR_RMS_MAXV)) return (int)hipErrorInvalidValue;
-  if (T == 1) return lin_rows_launch<1>(x, w, res, gain, y, T, C, K, pro, eps, s);
-  if (T == 2) return lin_rows_launch<2>(x, w, res, gain, y, T, C, K, pro, eps, s);
-  if (T <= 4) return lin_rows_launch<4>(x, w, res, gain, y, T, C, K, pro, eps, s);
-  if (T <= 8) return lin_rows_launch<8>(x, w, res, gain, y, T, C, K, pro, eps, s);
-  return lin_rows_launch<16>(x, w, res, gain, y, T, C, K, pro, eps, s);
+  if (!lin_rows_args_ok(x, w, gain, y, T, C, K, pro)) return (int)hipErrorInvalidValue;
+  return lin_rows_dispatch<false>(x, w, res, gain, y, T, C, K, pro, eps, LrLora{}, s);
+}
+
+static bool lr_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static bool lr_rank_ok(int r) { return r == 4 || r == 8 || r == 16; }
+
+// ddl_lin_rows_f32 with the adapter's expand fused into the epilogue: the lane that owns (t, k) adds
+// scale * sum_j u[t][j] B[ids[t]][k][j] to the reduced sum before the residual. u [T][r] (16-byte
+// aligned), B [Rn][K][r] with slots b_stride floats apart, ids int32 [T]. A row whose id is outside
+// [0, Rn) takes ddl_lin_rows_f32's own expression and has its bits.
+DDL_API int ddl_lin_rows_lora_f32(const float* x, const float* w, const float* res, const float* gain, float* y,
+                                  int T, int C, int K, int pro, float eps, const float* u, const float* B,
+                                  const int* ids, int Rn, long long b_stride, int r, float scale, hipStream_t s) {
+  if (!lin_rows_args_ok(x, w, gain, y, T, C, K, pro)) return (int)hipErrorInvalidValue;
+  if (!u || !B || !ids || Rn < 1 || !lr_rank_ok(r) || !lr_al16(u) || !lr_al16(B)) return (int)hipErrorInvalidValue;
+  if (b_stride % 4 || (Rn > 1 && b_stride < (long long)K * r)) return (int)hipErrorInvalidValue;
+  const LrLora lo{u, B, ids, b_stride, Rn, r, scale};
+  return lin_rows_dispatch<true>(x, w, res, gain, y, T, C, K, pro, eps, lo, s);
+}
+
+// The adapter's shrink: u[t][j] = pro(x)[t] . A[ids[t]][j]. One workgroup per row: the row staged by
+// lr_stage (the bits ddl_lin_rows_f32 stages), wave w takes ranks w, w + 4, ..; each lane an fmaf
+// chain over its float4 chunks, then the wave butterfly. No adapter: the row of u is zero.
+template <int NR>
+__global__ __launch_bounds__(256) void lora_rows_u_kernel(const float* __restrict__ x, const float* __restrict__ A,
+                                                          const int* __restrict__ ids,
+                                                          const float* __restrict__ gain, float* __restrict__ u,
+                                                          int C, int Rn, long long as, int pro, float eps) {
+  extern __shared__ __attribute__((aligned(16))) float lr_xs[];  // [C]
+  constexpr int r = 4 * NR;
+  const int t = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int id = ids[t];  // in flight while the row is staged (x is valid whatever the id)
+  const int C4 = C / 4;
+  float4* xs4 = (float4*)lr_xs;
+  lr_stage<1>(x + (long long)t * (pro == LR_SWIGLU ? 2 * C : C), gain, xs4, 1, C, pro, eps);
+  __syncthreads();
+  if (id < 0 || id >= Rn) {  // uniform over the workgroup
+    if (threadIdx.x < r) u[(long long)t * r + threadIdx.x] = 0.f;
+    return;
+  }
+  const float* a0 = A + (long long)id * as;
+  float acc[NR];
+#pragma unroll
+  for (int m = 0; m < NR; ++m) acc[m] = 0.f;
+  for (int c = lane; c < C4; c += 64) {
+    const float4 xv = xs4[c];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const float4 av = ((const float4*)(a0 + (long long)(wv + 4 * m) * C))[c];
+      float a = acc[m];
+      a = fmaf(av.x, xv.x, a);
+      a = fmaf(av.y, xv.y, a);
+      a = fmaf(av.z, xv.z, a);
+      a = fmaf(av.w, xv.w, a);
+      acc[m] = a;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < NR; ++m) {
+    const float s = wave_sum(acc[m]);
+    if (lane == 0) u[(long long)t * r + wv + 4 * m] = s;
+  }
+}
+
+// x [T][C] ([T][2C] for swiglu), A [Rn][r][C] with slots a_stride floats apart (0: one shared A),
+// ids int32 [T], u [T][r]. r in {4, 8, 16}, 1 <= T <= 16, C % 4 == 0.
+DDL_API int ddl_lora_rows_u(const float* x, const float* A, const int* ids, const float* gain, float* u, int T, int C,
+                            int Rn, int r, long long a_stride, int pro, float eps, hipStream_t s) {
+  if (!lin_rows_args_ok(x, A, gain, u, T, C, 1, pro)) return (int)hipErrorInvalidValue;
+  if (!ids || Rn < 1 || !lr_rank_ok(r) || !lr_al16(x) || !lr_al16(A) || !lr_al16(u)) return (int)hipErrorInvalidValue;
+  if (a_stride % 4 || (a_stride != 0 && a_stride < (long long)r * C)) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)C * sizeof(float);
+  if (lds > (size_t)LR_LDS_BYTES) return (int)hipErrorInvalidValue;
+#define LR_U(NR)                                                                                                  \
+  hipLaunchKernelGGL(lora_rows_u_kernel<NR>, dim3(T), dim3(256), lds, s, x, A, ids, gain, u, C, Rn, a_stride, pro, eps)
+  if (r == 4) LR_U(1);
+  else if (r == 8) LR_U(2);
+  else LR_U(4);
+#undef LR_U
+  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

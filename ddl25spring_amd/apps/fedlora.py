@@ -6,7 +6,10 @@
 Every round writes one JSONL record: ``round``, ``heldout_loss`` (per dialect; round 0 is the base
 model), ``round_time``, ``tokens``, ``tokens_per_s``, ``message_count`` and, with ``--report-gap``,
 ``gap`` and ``mean_merged_loss``. ``--sample-tokens N`` continues held-out prompts with the merged
-global adapter at the end (``samples`` in the final record)."""
+global adapter at the end (``samples`` in the final record). ``--sample-adapters clients`` instead
+continues, for each client of the last round, one held-out prompt of its grammar under the base
+model, the global adapter and the client's own upload, batched through per-sequence adapters with
+nothing merged; each sample is then ``{client, dialect, adapter, tokens}``."""
 from __future__ import annotations
 
 from ..fl.lora import FedLoRA, FedLoRAConfig, FedLoRAResult  # noqa: F401  (the CLI reads the config here)

@@ -38,6 +38,8 @@ from .aggregate import aggregate_into, make_aggregator
 
 CLIENT_SPAN = 1 << 20   # sequence indices reserved per client of a grammar
 HELDOUT_START = 1 << 40  # the held-out block of every grammar: beyond any client's span
+SAMPLE_ADAPTERS = ("global", "clients")
+SAMPLE_CHUNK = 16        # sequences per generate call of the "clients" samples: the skinny decode path
 
 
 @dataclass
@@ -88,6 +90,10 @@ class FedLoRAConfig:
     # after the last round: continue held-out prompts with the merged model
     sample_tokens: int = 0
     sample_prompt_len: int = 8
+    # "global": the merged global adapter on every grammar's prompts; "clients": for each client of the
+    # last round one held-out prompt of its grammar under the base, the global and the client's own
+    # adapter, batched through per-sequence adapters (nothing is merged)
+    sample_adapters: str = "global"
     jsonl: str | None = None
     checkpoint: str | None = None
     seed: int = 0
@@ -165,6 +171,8 @@ class FedLoRA:
             raise ValueError("fedlora: clients, slots, local_steps, batch_size and dialects must be at least 1")
         if cfg.dialects > cfg.clients:
             raise ValueError(f"fedlora: {cfg.dialects} dialects for {cfg.clients} clients")
+        if cfg.sample_adapters not in SAMPLE_ADAPTERS:
+            raise ValueError(f"fedlora: sample_adapters {cfg.sample_adapters!r} not in {SAMPLE_ADAPTERS}")
         self.dev = self.ctx.device
         self.N, self.C = cfg.clients, cfg.client_fraction
         self.K = max(1, round(cfg.client_fraction * self.N))
@@ -196,6 +204,9 @@ class FedLoRA:
         self.round_idx = 0
         self.waves_last_round = 0
         self.records: list[dict] = []
+        # sample_adapters = "clients": the last round's clients and their rows as uploaded
+        self.last_clients: list[int] = []
+        self.client_rows = None
 
     # ------------------------------------------------------------------------------------ data
     def client_batch(self, client: int, round_idx: int, step: int) -> np.ndarray:
@@ -293,6 +304,9 @@ class FedLoRA:
             self.rows[w * self.S:w * self.S + len(clients)].copy_(self.opt.data[:len(clients)])
         self.waves_last_round = len(waves)
         mean_prod = self._client_products(self.rows) if cfg.report_gap else None
+        if cfg.sample_adapters == "clients":  # before the aggregation: some rules rewrite the rows
+            self.client_rows = self.rows.clone()
+            self.last_clients = chosen
         aggregate_into(self.aggregator, self.ctx, self.rows, self.coeffs, self.global_row, center=self.global_row,
                        counts=[self.K], keys=list(range(self.K)))
         self.round_idx += 1
@@ -345,7 +359,10 @@ class FedLoRA:
     @torch.no_grad()
     def sample(self, n_tokens: int, prompt_len: int = 8):
         """Continue the first ``prompt_len`` tokens of a held-out batch of every grammar by ``n_tokens``
-        greedy tokens with the merged global adapter -> [[token ids]]."""
+        greedy tokens with the merged global adapter -> [[token ids]]. With
+        ``sample_adapters = "clients"``: ``sample_clients``."""
+        if self.cfg.sample_adapters == "clients":
+            return self.sample_clients(n_tokens, prompt_len)
         out = []
         merge_lora(self.model, self.global_row)
         try:
@@ -354,6 +371,32 @@ class FedLoRA:
                 out.extend(self.model.generate(prompt, max_new_tokens=n_tokens, seed=self.cfg.seed).cpu().tolist())
         finally:
             unmerge_lora(self.model)
+        return out
+
+    @torch.no_grad()
+    def sample_clients(self, n_tokens: int, prompt_len: int = 8):
+        """For each client of the last round: one held-out prompt of the client's grammar, continued
+        by ``n_tokens`` greedy tokens under the base model, the global adapter and the client's own
+        upload -> [{client, dialect, adapter, tokens}]. One adapter bank ``[global; client rows]``
+        and per-sequence adapter ids, ``SAMPLE_CHUNK`` sequences per ``generate``; nothing is merged.
+        (The client rows are those of a round run by this object: none after a bare resume.)"""
+        from ..models.lora import adapter_bank
+        if not self.last_clients:
+            return []
+        bank = adapter_bank(self.model, torch.cat([self.global_row[None], self.client_rows]))
+        jobs = []  # (prompt [prompt_len], adapter id, labels)
+        for j, c in enumerate(self.last_clients):
+            d = c % self.cfg.dialects
+            batch = self.heldout_batch(d, self.cfg.eval_batches)
+            prompt = batch[j % batch.shape[0], :prompt_len]
+            for label, aid in (("base", -1), ("global", 0), ("client", 1 + j)):
+                jobs.append((prompt, aid, dict(client=c, dialect=d, adapter=label)))
+        out = []
+        for i in range(0, len(jobs), SAMPLE_CHUNK):
+            chunk = jobs[i:i + SAMPLE_CHUNK]
+            toks = self.model.generate(torch.stack([p for p, _, _ in chunk]).to(self.dev), max_new_tokens=n_tokens,
+                                       seed=self.cfg.seed, adapters=bank, adapter_ids=[a for _, a, _ in chunk])
+            out.extend(dict(lab, tokens=t) for (_, _, lab), t in zip(chunk, toks.cpu().tolist()))
         return out
 
     # ---------------------------------------------------------------------- checkpoint / resume

@@ -196,25 +196,43 @@ class LLama(nn.Module):
             raise NotImplementedError("generation from a tensor-parallel (sharded) model is not supported")
 
     @torch.no_grad()
-    def prefill(self, prompt_ids, prompt_lens, cache):
+    def _adapter_args(self, cache, adapters, adapter_ids):
+        """Validate ``adapters`` / ``adapter_ids`` (host side) and put the ids into ``cache.aid``;
+        with ids of None the cache keeps the ids it has."""
+        if adapters is None:
+            if adapter_ids is not None:
+                raise ValueError("generation: adapter_ids without adapters")
+            return
+        adapters.check(self, cache.device)
+        if adapter_ids is not None:
+            cache.set_adapter_ids(adapter_ids, adapters.R)
+
+    @torch.no_grad()
+    def prefill(self, prompt_ids, prompt_lens, cache, adapters=None, adapter_ids=None):
         """Right-padded prompts [B, T] (real lengths ``prompt_lens`` [B]) through the blocks once:
         every layer's K (rotated) and V go into ``cache``, ``cache.lens = prompt_lens``; returns
-        the logits of each sequence's last real position, [B, V] (``cache.logits``)."""
+        the logits of each sequence's last real position, [B, V] (``cache.logits``). ``adapters``
+        (an ``AdapterBank``): sequence b runs adapter ``adapter_ids[b]`` (-1: the base model)."""
         from ..ops import llama_decode as D
         self._check_generation()
+        self._adapter_args(cache, adapters, adapter_ids)
         B, T = prompt_ids.shape
         if B != cache.batch or T > cache.max_len:
             raise ValueError(f"prefill: prompts {B} x {T} do not fit the cache ({cache.batch} x {cache.max_len})")
         dev = cache.device
         lens = torch.as_tensor(prompt_lens, dtype=torch.int32).to(dev)
         x = A.embedding(prompt_ids.to(dev), self.first.emb, self.first.padding_idx, dtype=torch.float32)
+        cache._gathered = None  # the bank's rows may have changed in place since the last prompts
+        lo = cache.gathered(adapters)  # per-sequence (A, B) pairs, gathered once (identity without adapters)
         for i, blk in enumerate(self.blocks()):
             h, x = A.rmsnorm_fork(x, blk.norm1)
-            qkv = A.linear(h, blk.wqkv)
+            qkv = lo(i, "wqkv", A.linear(h, blk.wqkv), h)
             D.kv_append(qkv, cache.k(i), cache.v(i), cache.cos, cache.sin, 0)
-            x = A.linear(A.causal_attention(qkv, blk.h, blk.hd), blk.wo, residual=x)
+            att = A.causal_attention(qkv, blk.h, blk.hd)
+            x = lo(i, "wo", A.linear(att, blk.wo, residual=x), att)
             h, x = A.rmsnorm_fork(x, blk.norm2)
-            x = A.linear(A.swiglu(A.linear(h, blk.w13)), blk.w2, residual=x)
+            g = A.swiglu(lo(i, "w13", A.linear(h, blk.w13), h))
+            x = lo(i, "w2", A.linear(g, blk.w2, residual=x), g)
         last = x[torch.arange(B, device=dev), (lens - 1).long()].contiguous()  # [B, D], no host sync
         if B <= D.LIN_ROWS_MAX_T:
             D.lin_rows(last, self.last.head.detach(), cache.logits, pro="rmsnorm", gain=self.last.norm.detach())
@@ -226,39 +244,53 @@ class LLama(nn.Module):
         return cache.logits
 
     @torch.no_grad()
-    def decode_step(self, cache, tokens=None, fused: bool = True, advance=None):
+    def decode_step(self, cache, tokens=None, fused: bool = True, advance=None, adapters=None, adapter_ids=None):
         """One token per sequence through the cached model: ``tokens`` [B] (forced decoding) or
         ``cache.next_tok``. Launches: the embedding; per layer norm+qkv, attention with the cache
         append, wo+residual, norm+w13, swiglu+w2+residual; norm+head. ``fused=False`` runs the
         existing rmsnorm / swiglu kernels before plain skinny linears (A/B and cross-check).
         Returns the static [B, V] logits buffer. ``advance`` (default: when ``tokens`` are given)
-        adds the appended row to ``cache.lens`` here; in ``generate`` the sampler does."""
+        adds the appended row to ``cache.lens`` here; in ``generate`` the sampler does.
+        ``adapters`` (an ``AdapterBank``): row b runs adapter ``cache.aid[b]`` (set from
+        ``adapter_ids`` when given; -1: the base row, bit for bit) — one more launch per adapted
+        linear, the shrink ``lora_rows_u``; the expand rides in the linear's epilogue."""
         from ..ops import llama_decode as D
         self._check_generation()
         c = cache
+        self._adapter_args(c, adapters, adapter_ids)
         if tokens is not None:
             if not tokens.is_cuda and (int(tokens.min()) < 0 or int(tokens.max()) >= self.first.vocab_size):
                 raise ValueError(f"decode_step: token outside [0, {self.first.vocab_size})")
             c.next_tok.copy_(tokens.to(torch.int32))
         c.embed(self.first.emb.detach())
         if c.batch > D.LIN_ROWS_MAX_T:
-            self._decode_wide(c)
+            self._decode_wide(c, adapters)
         else:
             xa, xb = c.xa, c.xb
+            u = None if adapters is None else c.u_rows(adapters.rank)
+
+            def lin(i, name, x, w, out, residual=None, pro="none", gain=None):
+                pair = None if adapters is None else adapters.pair(i, name)
+                lora = None
+                if pair is not None:  # the shrink on the rows the linear stages, then the fused expand
+                    D.lora_rows_u(x, pair[0], c.aid, u, pro, gain)
+                    lora = (u, pair[1], c.aid, adapters.scale)
+                D.lin_rows(x, w.detach(), out, residual, pro, gain, lora=lora)
+
             for i, blk in enumerate(self.blocks()):
                 n1, n2 = blk.norm1.detach(), blk.norm2.detach()
                 if fused:
-                    D.lin_rows(xa, blk.wqkv.detach(), c.qkv, pro="rmsnorm", gain=n1)
+                    lin(i, "wqkv", xa, blk.wqkv, c.qkv, pro="rmsnorm", gain=n1)
                 else:
-                    D.lin_rows(c.rmsnorm(xa, n1), blk.wqkv.detach(), c.qkv)
+                    lin(i, "wqkv", c.rmsnorm(xa, n1), blk.wqkv, c.qkv)
                 D.attn_decode(c.qkv, c.k(i), c.v(i), c.lens, c.cos, c.sin, c.att, c.splits, c.ws)
-                D.lin_rows(c.att, blk.wo.detach(), xb, residual=xa)
+                lin(i, "wo", c.att, blk.wo, xb, residual=xa)
                 if fused:
-                    D.lin_rows(xb, blk.w13.detach(), c.h13, pro="rmsnorm", gain=n2)
-                    D.lin_rows(c.h13, blk.w2.detach(), xa, residual=xb, pro="swiglu")
+                    lin(i, "w13", xb, blk.w13, c.h13, pro="rmsnorm", gain=n2)
+                    lin(i, "w2", c.h13, blk.w2, xa, residual=xb, pro="swiglu")
                 else:
-                    D.lin_rows(c.rmsnorm(xb, n2), blk.w13.detach(), c.h13)
-                    D.lin_rows(c.swiglu(c.h13), blk.w2.detach(), xa, residual=xb)
+                    lin(i, "w13", c.rmsnorm(xb, n2), blk.w13, c.h13)
+                    lin(i, "w2", c.swiglu(c.h13), blk.w2, xa, residual=xb)
             if fused:
                 D.lin_rows(xa, self.last.head.detach(), c.logits, pro="rmsnorm", gain=self.last.norm.detach())
             else:
@@ -267,22 +299,27 @@ class LLama(nn.Module):
             c.lens.add_((c.lens < c.max_len).to(torch.int32))
         return c.logits
 
-    def _decode_wide(self, c):
-        """More than 16 sequences: the linears on the training engine (``A.linear``); the decode
+    def _decode_wide(self, c, adapters=None):
+        """More than 16 sequences: the linears on the training engine (``A.linear``), the adapters
+        through the training product (``lora_fwd``) on per-sequence gathered pairs; the decode
         attention and the sampler have no such limit."""
         from ..ops import llama_decode as D
         x = c.xa
+        lo = c.gathered(adapters)
         for i, blk in enumerate(self.blocks()):
-            c.qkv.copy_(A.linear(A.rmsnorm(x, blk.norm1), blk.wqkv))
+            h = A.rmsnorm(x, blk.norm1)
+            c.qkv.copy_(lo(i, "wqkv", A.linear(h, blk.wqkv), h))
             D.attn_decode(c.qkv, c.k(i), c.v(i), c.lens, c.cos, c.sin, c.att, c.splits, c.ws)
-            x = A.linear(c.att, blk.wo, residual=x)
-            x = A.linear(A.swiglu(A.linear(A.rmsnorm(x, blk.norm2), blk.w13)), blk.w2, residual=x)
+            x = lo(i, "wo", A.linear(c.att, blk.wo, residual=x), c.att)
+            h = A.rmsnorm(x, blk.norm2)
+            g = A.swiglu(lo(i, "w13", A.linear(h, blk.w13), h))
+            x = lo(i, "w2", A.linear(g, blk.w2, residual=x), g)
         c.logits.copy_(A.linear(A.rmsnorm(x, self.last.norm), self.last.head))
 
     @torch.no_grad()
     def generate(self, prompt_ids, prompt_lens=None, max_new_tokens: int = 32, temperature: float = 0.0,
                  top_k: int = 0, seed: int = 0, eos_id=None, graph=None, fused=None, return_logits: bool = False,
-                 cache=None):
+                 cache=None, adapters=None, adapter_ids=None):
         """Continue right-padded prompts [B, T] by ``max_new_tokens`` tokens -> int64 [B, N]
         (``return_logits``: also the fp32 [B, N, V] logits each token was drawn from).
         ``temperature == 0`` is greedy; else temperature / ``top_k`` sampling, a pure function of
@@ -290,7 +327,12 @@ class LLama(nn.Module):
         steps whose state (token, lengths, finished flags, Philox counter) stays on the device:
         the loop never waits for the GPU, and with ``graph`` every step is one HIP-graph replay.
         ``cache``: a ``KVCache`` to reuse (its captured step included). Unset ``graph`` /
-        ``fused`` take ``GENERATE_DEFAULTS``."""
+        ``fused`` take ``GENERATE_DEFAULTS``. ``adapters`` (models/lora.py: ``adapter_bank``) with
+        ``adapter_ids`` [B] (a list or int tensor; -1 = the base model): sequence b is continued
+        under LoRA adapter ``adapter_ids[b]`` without merging anything. The captured step reads
+        the ids from the device, so one capture serves any later assignment and any in-place
+        change of the bank's rows. Without ``adapters`` the base model generates, adapters
+        attached or not."""
         from ..ops import llama_decode as D
         self._check_generation()
         if prompt_ids.dim() != 2 or prompt_ids.dtype not in (torch.int64, torch.int32):
@@ -321,6 +363,9 @@ class LLama(nn.Module):
             cache = KVCache(self, B, need)
         elif cache.batch != B or cache.max_len < need:
             raise ValueError(f"generate: the cache ({cache.batch} x {cache.max_len}) does not fit {B} x {need}")
+        if adapters is not None and adapter_ids is None:
+            raise ValueError("generate: adapters need adapter_ids [B] (-1: the base model)")
+        self._adapter_args(cache, adapters, adapter_ids)
         dev = cache.device
         on_gpu = dev.type == "cuda"
         fused = GENERATE_DEFAULTS["fused"] if fused is None else bool(fused)
@@ -330,16 +375,17 @@ class LLama(nn.Module):
         cache.out = out
 
         def one_step():
-            self.decode_step(cache, fused=fused)
+            self.decode_step(cache, fused=fused, adapters=adapters)
             D.sample(cache.logits, cache.next_tok, cache.out, cache.lens, cache.finished, cache.step,
                      cache.max_len, temperature, top_k, seed, eos, advance=True)
 
         step = one_step
         if graph:  # a captured step writes the token buffer it was recorded with, kept beside the graph
-            step = cache.captured_step((float(temperature), int(top_k), int(seed), eos, fused, N), one_step, N)
+            key = (float(temperature), int(top_k), int(seed), eos, fused, N)
+            step = cache.captured_step(key if adapters is None else key + adapters.key, one_step, N)
             out = cache.out
             out.zero_()
-        logits = self.prefill(prompt_ids, plens, cache)
+        logits = self.prefill(prompt_ids, plens, cache, adapters)
         all_logits = torch.empty(B, N, V, dtype=torch.float32, device=dev) if return_logits else None
         if return_logits:
             all_logits[:, 0].copy_(logits)
@@ -356,13 +402,19 @@ class LLama(nn.Module):
 # ``generate``'s defaults, as measured by benchmarks/bench_generate.py (profiles/generate.txt): the graph
 # replay is 1.9x the eager loop at B = 1 and level with it at B = 16, the fused prologues 6-14 % ahead
 GENERATE_DEFAULTS = {"graph": True, "fused": True}
+# Per-sequence adapters take the two-launch route (the shrink ``lora_rows_u``, then the expand in the
+# linear's epilogue), the only one built: 57 launches a step against 33, measured at +103 / +81 / +46 us
+# a step at B = 1 / 8 / 16 (benchmarks/bench_generate.py --adapters 8, profiles/adapter_generate.txt). A
+# one-launch variant that recomputes u in every workgroup was not built and is not a default.
 
 
 class KVCache:
     """Everything a decode step reads or writes, allocated once: one fp32 buffer
     [layers][2][B][H][max_len][hd] (K stored rotated), the device-side sequence state (``lens``,
     ``finished``, ``next_tok``, the per-row step counter ``step``; int32 [B]), RoPE tables of
-    ``max_len`` rows and the step's activation buffers."""
+    ``max_len`` rows and the step's activation buffers; for per-sequence adapters the ids ``aid``
+    (int32 [B], -1 = none) and one [B, 16] buffer for the shrink's ``u`` (the adapted linears run one
+    after another on one stream, so one buffer serves them all)."""
 
     def __init__(self, model: "LLama", batch: int, max_len: int):
         from ..ops import llama_decode as D
@@ -392,6 +444,9 @@ class KVCache:
         self.rstd = torch.zeros(batch, dtype=torch.float32, device=dev)
         self.splits = D.attn_splits(max_len)
         self.ws = D.attn_workspace(batch, H, hd, self.splits, dev)
+        self.aid = torch.full((batch,), -1, dtype=torch.int32, device=dev)
+        self.u = fbuf(D.LORA_RANKS[-1])
+        self._gathered = None
         self.out = None
         self._graphs: dict = {}
 
@@ -400,6 +455,45 @@ class KVCache:
 
     def v(self, layer: int):
         return self.kv[layer, 1]
+
+    # --- per-sequence adapters
+    def set_adapter_ids(self, adapter_ids, R: int):
+        """``adapter_ids`` (a list or int tensor [B], -1 = the base model) into ``aid``; values outside
+        ``[-1, R)`` raise here, on the host."""
+        ids = adapter_ids.tolist() if torch.is_tensor(adapter_ids) else list(adapter_ids)
+        if len(ids) != self.batch or any(int(v) != v or not -1 <= v < R for v in ids):
+            raise ValueError(f"adapter_ids {ids}: {self.batch} integers in [-1, {R}) expected")
+        self.aid.copy_(torch.tensor([int(v) for v in ids], dtype=torch.int32))
+        self._gathered = None
+
+    def u_rows(self, rank: int):
+        """The first B * rank floats of ``u`` as the shrink's [B, rank] output."""
+        return self.u.view(-1)[:self.batch * rank].view(self.batch, rank)
+
+    def gathered(self, bank):
+        """``f(block, target, y, x) -> y`` for the paths off the hot one (prefill, more than 16
+        sequences): y [B, ..., N] = the base linear of x [B, ..., D], with sequence b's adapter product
+        added in place by the training kernel (``ops.lora.lora_fwd`` with S = B) on pairs gathered
+        per sequence from ``aid`` (B zeroed where a sequence has no adapter). The gather is made once
+        per prefill or id assignment (a copy: rows rewritten in place show from the next one on); no
+        bank: the identity."""
+        if bank is None:
+            return lambda i, name, y, x: y
+        from ..ops import lora as L
+        if self._gathered is None or self._gathered[0] is not bank:
+            slot, has = self.aid.clamp(min=0).long(), (self.aid >= 0).to(torch.float32)[:, None, None]
+            self._gathered = (bank, {k: (a[slot].contiguous(), (b[slot] * has).contiguous())
+                                     for k, (a, b) in bank.pairs.items()})
+        pairs, nb = self._gathered[1], self.batch
+
+        def add(i, name, y, x):
+            pair = pairs.get((i, name))
+            if pair is not None:
+                L.lora_fwd(x.reshape(nb, -1, x.shape[-1]).contiguous(), pair[0], pair[1],
+                           y.view(nb, -1, y.shape[-1]), bank.scale)
+            return y
+
+        return add
 
     # the step's launches that are not in ops/llama_decode.py: existing kernels on static buffers
     def embed(self, emb):

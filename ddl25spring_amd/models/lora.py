@@ -12,6 +12,11 @@ strided views of its ``data [S, P]`` rows: row s is what client s uploads, and `
 aggregates the rows in place. ``freeze_a`` (FFA-LoRA, Sun et al. 2024) keeps A at its shared seed
 initialisation and out of the rows, which makes averaging the rows exact: mean(B_k) A = mean(B_k A).
 
+Generation with several adapters at once, nothing merged (``rows`` is any ``[R, P]`` stack of rows):
+
+    bank = adapter_bank(model, rows)
+    model.generate(prompts, adapters=bank, adapter_ids=[0, 2, -1, 1])   # -1: the base model
+
 Only the whole fp32 model in one process is supported; the embedding, the RMSNorm gains and the
 LM head stay frozen and unadapted.
 """
@@ -197,6 +202,65 @@ def _adapters(model) -> LoRAAdapters:
     if ad is None:
         raise RuntimeError("lora: the model has no adapters (attach_lora)")
     return ad
+
+
+class AdapterBank:
+    """R adapters for generation (``LLama.generate(adapters=bank, adapter_ids=...)``): per
+    (block, target) the strided views ``A [R, r, D]`` and ``B [R, N, r]`` into ``rows [R, P]``. The
+    views alias ``rows``: writing a row in place changes what the next step computes."""
+
+    def __init__(self, owner: LoRAAdapters, rows, pairs: dict):
+        self.owner, self.rows, self.pairs = owner, rows, pairs
+        self.R, self.rank, self.scale = int(rows.shape[0]), owner.cfg.rank, owner.cfg.scale
+        self.targets = tuple(owner.cfg.targets)
+
+    def pair(self, block: int, target: str):
+        """(A, B) of one targeted linear, or None where the target has no adapter."""
+        return self.pairs.get((block, target))
+
+    @property
+    def key(self):
+        """What a captured decode step depends on beside the ids (which it reads on the device)."""
+        return (self.rows.data_ptr(), self.R, int(self.rows.stride(0)), self.rank, self.targets)
+
+    def check(self, model, device):
+        if self.owner is not getattr(model, "lora", None):
+            raise ValueError("lora: the adapter bank belongs to another model")
+        if self.owner.merged:
+            raise RuntimeError("lora: an adapter is merged into the base weights (unmerge_lora first)")
+        if self.rows.device != device:
+            raise ValueError(f"lora: the adapter bank is on {self.rows.device}, the model on {device}")
+
+
+@torch.no_grad()
+def adapter_bank(model, rows) -> AdapterBank:
+    """Any stack ``rows [R, P]`` of ``SlotAdam`` rows (``opt.data``, ``global_row[None]``, a
+    ``torch.cat`` of them) on the model's device as per-sequence adapters of ``LLama.generate``. A
+    frozen A (FFA-LoRA) is the model's one shared copy, with slot stride 0."""
+    ad = _adapters(model)
+    if ad.merged:
+        raise RuntimeError("lora: an adapter is merged into the base weights (unmerge_lora first)")
+    opt = ad._opt()
+    dev = ad.parameters()[0].device
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] != opt.P:
+        raise ValueError(f"lora: adapter rows must be [R, {opt.P}]")
+    if rows.dtype != torch.float32 or rows.device != dev:
+        raise ValueError(f"lora: adapter rows must be float32 on {dev}")
+    if rows.stride(1) != 1 or rows.stride(0) % 4 or rows.data_ptr() % 16 or \
+            (rows.shape[0] > 1 and rows.stride(0) < opt.P):
+        raise ValueError(f"lora: adapter rows must be packed, 16-byte aligned rows (strides {rows.stride()})")
+    R = rows.shape[0]
+    views = {n: rows[:, off:off + p[0].numel()].view(R, *p.shape[1:])
+             for (n, p), off in zip(ad.trainable(), opt.offsets)}
+    pairs = {}
+    for i in range(len(model.blocks())):
+        for t in ad.cfg.targets:
+            a = views.get(f"{i}.{t}.A")
+            if a is None:
+                a0 = ad.named[f"{i}.{t}.A"].detach()[0]
+                a = a0.unsqueeze(0).expand(R, *a0.shape)
+            pairs[(i, t)] = (a, views[f"{i}.{t}.B"])
+    return AdapterBank(ad, rows, pairs)
 
 
 @torch.no_grad()

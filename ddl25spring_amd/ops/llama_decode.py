@@ -1,6 +1,8 @@
 """Ops of the fp32 LLaMA's generation path (csrc/kernels/llama_decode.hip): a skinny-row linear with
 fused prologues, single-query attention over a KV cache with the step's row appended in the same
-launch, the prefill's cache append, and a sampler that also carries the step's state.
+launch, the prefill's cache append, and a sampler that also carries the step's state. Per-sequence
+LoRA adapters (row t of the batch runs adapter ``ids[t]``): the shrink ``lora_rows_u`` and the expand
+fused into ``lin_rows(lora=...)``.
 
 Every function writes into caller-provided buffers (nothing is allocated inside a step, so a step
 can be captured into one HIP graph) and returns its output buffer. CPU tensors run the PyTorch fp32
@@ -25,15 +27,18 @@ from . import reference as ref
 from ._lib import check, ptr, stream
 from .llama_f32 import ATTN_HD
 
-vp, i32, f32, u64 = _lib.vp, _lib.i32, _lib.f32, _lib.u64
+vp, i32, i64, f32, u64 = _lib.vp, _lib.i32, _lib.i64, _lib.f32, _lib.u64
 _lib.register_signatures({
     "ddl_lin_rows_f32": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "ddl_lin_rows_lora_f32": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, i64, i32, f32, vp],
+    "ddl_lora_rows_u": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, f32, vp],
     "ddl_attnf_decode": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp],
     "ddl_kv_append": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "ddl_sample_f32": [vp, i32, i32, f32, i32, u64, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
 })
 
 LIN_ROWS_MAX_T = 16
+LORA_RANKS = (4, 8, 16)  # ranks of the per-sequence adapters (ops/lora.py: RANKS)
 TOP_K_MAX = 1024
 PROLOGUES = {"none": 0, "rmsnorm": 1, "swiglu": 2}
 ATTN_REC_EXTRA = 2  # floats of a split record beside its HD accumulators: max, sum
@@ -44,32 +49,97 @@ def K():
 
 
 # --------------------------------------------------------------------------------- lin_rows
-def lin_rows_launch(x, w, out, residual=None, pro="none", gain=None, eps=1e-6, T=None, C=None) -> int:
+def _slot_stride(t) -> int:
+    """Slot stride in floats of an adapter view [R, a, b] (0: one shared slot)."""
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1] * t.shape[2])
+
+
+def lin_rows_launch(x, w, out, residual=None, pro="none", gain=None, eps=1e-6, T=None, C=None, lora=None,
+                    rank=None) -> int:
     """The raw launcher's return code (0, or hipErrorInvalidValue without a launch)."""
     Kout = w.shape[0]
     T = x.shape[0] if T is None else T
     C = w.shape[1] if C is None else C
+    if lora is not None:
+        u, B, ids, scale = lora
+        return int(K().ddl_lin_rows_lora_f32(ptr(x), ptr(w), ptr(residual), ptr(gain), ptr(out), T, C, Kout,
+                                             PROLOGUES[pro], float(eps), ptr(u), ptr(B), ptr(ids), B.shape[0],
+                                             _slot_stride(B), B.shape[2] if rank is None else rank, float(scale),
+                                             stream()))
     return int(K().ddl_lin_rows_f32(ptr(x), ptr(w), ptr(residual), ptr(gain), ptr(out), T, C, Kout,
                                     PROLOGUES[pro], float(eps), stream()))
 
 
-def lin_rows_ref(x, w, residual=None, pro="none", gain=None, eps=1e-6):
+def _prologue_ref(x, pro, gain, eps):
     if pro == "rmsnorm":
         x = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * gain
     elif pro == "swiglu":
         a, b = x.chunk(2, -1)
         x = torch.nn.functional.silu(a) * b
-    y = x @ w.t()
+    return x
+
+
+def _valid_ids(ids, R):
+    """(bool [T]: the row has an adapter, int64 [T]: its slot, 0 where it has none)."""
+    ok = (ids >= 0) & (ids < R)
+    return ok, torch.where(ok, ids, torch.zeros_like(ids)).long()
+
+
+def lin_rows_ref(x, w, residual=None, pro="none", gain=None, eps=1e-6, lora=None):
+    y = _prologue_ref(x, pro, gain, eps) @ w.t()
+    if lora is not None:
+        u, B, ids, scale = lora
+        ok, slot = _valid_ids(ids, B.shape[0])
+        d = torch.einsum("tj,tkj->tk", u, B[slot])
+        y = torch.where(ok[:, None], y + float(scale) * d, y)
     return y if residual is None else y + residual
 
 
-def lin_rows(x, w, out, residual=None, pro="none", gain=None, eps=1e-6):
+def _check_ids(name, ids, T):
+    if ids.dtype != torch.int32 or tuple(ids.shape) != (T,) or not ids.is_contiguous():
+        raise ValueError(f"{name}: ids must be a contiguous int32 [{T}] tensor")
+
+
+def _check_slots(name, what, t, shape, shared_ok):
+    """An adapter view [R, a, b]: fp32, packed inside a slot, slots 16-byte aligned (stride 0 = one
+    shared slot where ``shared_ok``)."""
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    R, a, b = shape
+    if t.stride(2) != 1 or t.stride(1) != b:
+        raise ValueError(f"{name}: {what} must be packed inside a slot (strides {t.stride()})")
+    ss = _slot_stride(t)
+    if ss % 4 or t.data_ptr() % 16 or not (ss >= a * b or (shared_ok and ss == 0)):
+        raise ValueError(f"{name}: {what} slots must be 16-byte aligned and not overlap (slot stride {ss})")
+
+
+def _check_lora(name, T, Kout, lora, like):
+    u, B, ids, _ = lora
+    if not 1 <= T <= LIN_ROWS_MAX_T:
+        raise ValueError(f"{name}: {T} rows (1 <= T <= {LIN_ROWS_MAX_T})")
+    if B.dim() != 3 or B.shape[2] not in LORA_RANKS:
+        raise ValueError(f"{name}: B must be [R, K, r] with r in {LORA_RANKS}")
+    r = B.shape[2]
+    _check_slots(name, "B", B, (B.shape[0], Kout, r), False)
+    _check_ids(name, ids, T)
+    if u.dtype != torch.float32 or tuple(u.shape) != (T, r) or not u.is_contiguous() or u.data_ptr() % 16:
+        raise ValueError(f"{name}: u must be a contiguous 16-byte aligned fp32 [{T}, {r}] tensor")
+    if len({like.device, u.device, B.device, ids.device}) != 1:
+        raise ValueError(f"{name}: operands on different devices")
+
+
+def lin_rows(x, w, out, residual=None, pro="none", gain=None, eps=1e-6, lora=None):
     """out[T, K] = pro(x)[T, C] @ w[K, C]^T (+ residual[T, K]), 1 <= T <= 16, C % 4 == 0.
-    ``pro``: "none"; "rmsnorm" (``gain`` [C], ``eps``); "swiglu" (x is [T, 2C] = [a | b])."""
+    ``pro``: "none"; "rmsnorm" (``gain`` [C], ``eps``); "swiglu" (x is [T, 2C] = [a | b]).
+    ``lora = (u, B, ids, scale)``: row t also gets ``scale * u[t] @ B[ids[t]]^T`` before the residual
+    (u [T, r] from ``lora_rows_u``, B [R, K, r] with any slot stride, ids int32 [T]); a row whose id
+    is outside ``[0, R)`` is the plain row, bit for bit."""
     if pro not in PROLOGUES:
         raise ValueError(f"lin_rows: prologue {pro!r} not in {tuple(PROLOGUES)}")
+    if lora is not None:
+        _check_lora("lin_rows", x.shape[0], w.shape[0], lora, x)
     if not x.is_cuda:
-        out.copy_(lin_rows_ref(x, w, residual, pro, gain, eps))
+        out.copy_(lin_rows_ref(x, w, residual, pro, gain, eps, lora))
         return out
     T, Cx = x.shape
     Kout, C = w.shape
@@ -78,8 +148,54 @@ def lin_rows(x, w, out, residual=None, pro="none", gain=None, eps=1e-6):
     for t in (x, w, out, residual, gain):
         if t is not None and not (t.is_contiguous() and t.dtype == torch.float32):
             raise ValueError("lin_rows: contiguous fp32 tensors only")
-    check(lin_rows_launch(x, w, out, residual, pro, gain, eps), "lin_rows_f32")
+    check(lin_rows_launch(x, w, out, residual, pro, gain, eps, lora=lora), "lin_rows_f32")
     return out
+
+
+# ----------------------------------------------------------------- per-sequence adapters: shrink
+def lora_rows_u_launch(x, A, ids, u, pro="none", gain=None, eps=1e-6, T=None, rank=None) -> int:
+    """The raw launcher's return code (0, or hipErrorInvalidValue without a launch)."""
+    R, r, C = A.shape
+    return int(K().ddl_lora_rows_u(ptr(x), ptr(A), ptr(ids), ptr(gain), ptr(u), x.shape[0] if T is None else T, C, R,
+                                   r if rank is None else rank, _slot_stride(A) if A.stride(0) else 0,
+                                   PROLOGUES[pro], float(eps), stream()))
+
+
+def lora_rows_u_ref(x, A, ids, pro="none", gain=None, eps=1e-6):
+    ok, slot = _valid_ids(ids, A.shape[0])
+    u = torch.einsum("tc,tjc->tj", _prologue_ref(x, pro, gain, eps), A[slot])
+    return torch.where(ok[:, None], u, torch.zeros_like(u))
+
+
+def lora_rows_u(x, A, ids, u, pro="none", gain=None, eps=1e-6):
+    """u[T, r] = pro(x)[T, C] @ A[ids[t]]^T: the adapters' shrink on the rows ``lin_rows`` stages
+    (the same prologues, the same staged bits). A [R, r, C] with any slot stride (a view into
+    optimizer rows; stride 0 = one shared A), ids int32 [T]; an id outside ``[0, R)`` means no
+    adapter and gives a zero row. r in (4, 8, 16), 1 <= T <= 16, C % 4 == 0."""
+    if pro not in PROLOGUES:
+        raise ValueError(f"lora_rows_u: prologue {pro!r} not in {tuple(PROLOGUES)}")
+    if A.dim() != 3 or A.shape[1] not in LORA_RANKS or x.dim() != 2:
+        raise ValueError(f"lora_rows_u: A must be [R, r, C] with r in {LORA_RANKS}, x [T, C]")
+    R, r, C = A.shape
+    T, Cx = x.shape
+    if not 1 <= T <= LIN_ROWS_MAX_T or C < 4 or C % 4 or Cx != (2 * C if pro == "swiglu" else C):
+        raise ValueError(f"lora_rows_u: x {tuple(x.shape)}, A {tuple(A.shape)} ({pro}); 1 <= T <= {LIN_ROWS_MAX_T}")
+    _check_slots("lora_rows_u", "A", A, (R, r, C), True)
+    _check_ids("lora_rows_u", ids, T)
+    if u.dtype != torch.float32 or tuple(u.shape) != (T, r) or not u.is_contiguous() or u.data_ptr() % 16:
+        raise ValueError(f"lora_rows_u: u must be a contiguous 16-byte aligned fp32 [{T}, {r}] tensor")
+    for t in (x, gain):
+        if t is not None and not (t.is_contiguous() and t.dtype == torch.float32 and t.data_ptr() % 16 == 0):
+            raise ValueError("lora_rows_u: contiguous 16-byte aligned fp32 tensors only")
+    if pro == "rmsnorm" and (gain is None or gain.numel() != C):
+        raise ValueError("lora_rows_u: the rmsnorm prologue needs gain [C]")
+    if len({x.device, A.device, ids.device, u.device}) != 1:
+        raise ValueError("lora_rows_u: operands on different devices")
+    if not x.is_cuda:
+        u.copy_(lora_rows_u_ref(x, A, ids, pro, gain, eps))
+        return u
+    check(lora_rows_u_launch(x, A, ids, u, pro, gain, eps), "lora_rows_u")
+    return u
 
 
 # --------------------------------------------------------------------------- decode attention
